@@ -22,11 +22,23 @@ flat-arena data-parallel engine on the plain-ATen model, tiny default shape):
 
 Every timed step is a full training step: H2D-free synthetic batch already
 resident (data="synthetic"), forward, loss, backward, gradient all-reduce,
-optimizer step.  After the timed region (not timed): a few steps with
-hipEvents around the all-reduce join (``exposed_allreduce_ms``), the
-cross-rank replica fingerprint check (``replicas_consistent``) and the peak
-HBM of the run.  ``--impl torch`` measures the stock PyTorch-ROCm reference
-stack (MIOpen convs + torch DDP) on the same config for comparison.
+optimizer step.  A plain run does nothing else: set up, W warm-up steps, the K
+timed steps, the JSON line.  ``--full`` adds, after the timed region (not
+timed): a few steps with hipEvents around the all-reduce join
+(``exposed_allreduce_ms``, per-bucket ``allreduce_timeline``), the cross-rank
+replica fingerprint check (``replicas_consistent``; diverged replicas exit
+non-zero), the reducer's description and the peak HBM of the run.
+``--impl torch`` measures the stock PyTorch-ROCm reference stack (MIOpen convs
++ torch DDP) on the same config for comparison.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step
+handed its caller, as float32 ``DIR/<name>.npy`` (``sample_index`` float64;
+rank 0's replica): train mode
+``loss`` (the step's return value) and a fixed seeded sample of the updated
+parameters (``params``) and of their gradients (``grads``), gathered in
+``model.parameters()`` order at the element indices in ``sample_index``; infer
+mode ``density`` (the estimated density maps).  Weights, batches and the sample
+are seeded, so two builds run with the same arguments compare file for file.
 """
 from __future__ import annotations
 
@@ -71,7 +83,13 @@ def parse(argv=None):
                    help="hipGraph-capture the step (hip impl): 1 always, 0 never (default: the eager step is faster "
                         "at batch 8 and at batch 1, profiles/r4, profiles/r5), auto for per-GPU inputs <= 2 x 768x1024 "
                         "pixels (engine/native.py AUTO_GRAPH_PIXELS)")
-    p.add_argument("--comm-steps", type=int, default=3, help="extra untimed steps with all-reduce timing events")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the untimed diagnostics (all-reduce timing steps, replica "
+                        "consistency check, reducer description, peak HBM) and report them in the JSON line")
+    p.add_argument("--comm-steps", type=int, default=3,
+                   help="--full: extra untimed steps with all-reduce timing events")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     p.add_argument("--mode", choices=["train", "infer"], default="train",
                    help="train: the headline training step; infer: forward-only density estimation (serving)")
     # test-only: rank 1 perturbs one weight of its replica after the timed steps, so the replica check must fail
@@ -157,6 +175,41 @@ def launch_ranks(a) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_SAMPLE = 1 << 21      # elements per sampled array: 8 MB of float32 each, far below the 64 MB a dump may take
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """``path/<name>.npy`` per array, float32 (float64 inputs stay float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if isinstance(t, torch.Tensor):
+            t = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(t))
+
+
+def train_outputs(trainer, loss) -> dict:
+    """What the last step handed its caller: the returned loss, and the parameters it updated in place with their
+    gradients -- every element when that fits DUMP_SAMPLE, else the elements at a fixed seeded sample of indices into
+    the concatenation of ``model.parameters()`` (independent of the arena's layout)."""
+    import numpy as np
+    import torch
+    params = list(trainer.model.parameters())
+    total = sum(p.numel() for p in params)
+    if total <= DUMP_SAMPLE:
+        index = np.arange(total, dtype=np.int64)
+    else:
+        index = np.sort(np.random.default_rng(0).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+    idx = torch.from_numpy(index).to(params[0].device)
+
+    def sample(ts):
+        return torch.cat([t.detach().reshape(-1).float() for t in ts])[idx]
+    return {"loss": loss.detach().reshape(-1), "params": sample(params),
+            "grads": sample([p.grad if p.grad is not None else torch.zeros_like(p) for p in params]),
+            "sample_index": index.astype(np.float64)}
+
+
 def infer(a, trainer, pool, sync_all, world, rank, local, dev, cpu) -> int:
     """Forward-only throughput (test.py's density estimation): eval mode, no autograd, the same kernels as the
     training forward (native: executor.forward_eval + the 1x1 head)."""
@@ -185,6 +238,8 @@ def infer(a, trainer, pool, sync_all, world, rank, local, dev, cpu) -> int:
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"density": et})
     if rank == 0:
         print(json.dumps({
             "metric": "CANNet inference imgs/sec (forward only, density map)", "value": round(a.batch * world * a.steps / dt, 3),
@@ -198,6 +253,58 @@ def infer(a, trainer, pool, sync_all, world, rank, local, dev, cpu) -> int:
         dist.barrier(**({} if cpu else {"device_ids": [local]}))
         dist.destroy_process_group()
     return 0
+
+
+def diagnostics(a, trainer, pool, sync_all, world, rank, dev, cpu, graph_used) -> dict:
+    """--full: the untimed diagnostics after the timed region (extra fields of the JSON line)."""
+    import torch
+    import torch.distributed as dist
+    extra = {}
+    red = getattr(trainer, "reducer", None)
+    native = a.impl == "hip" and a.dtype != "fp32"       # hip + fp32 = split-bf16 convs under the torch step
+    if native or a.impl == "arena":
+        extra["reducer"] = None if red is None else red.transport
+        if native:
+            extra["rccl_world"] = (red.comm.world if (red is not None and red.comm is not None) else
+                                   (1 if red is None else None))
+            # the all-reduce's CU budget (ncclConfig_t.minCTAs = maxCTAs; 0 = RCCL's default; None: no owned comm)
+            extra["comm_ctas"] = None if red is None else red.comm_ctas
+        extra["buckets_mib"] = None if red is None else [round(b.numel * 4 / 2 ** 20, 3) for b in red.buckets]
+        if a.comm_steps > 0 and not graph_used:
+            trainer.comm_timing = True
+            for i in range(a.comm_steps):
+                trainer.step(*pool[i % len(pool)])
+            trainer.comm_timing = False
+            if native:
+                ms_comm = trainer.exposed_comm_ms()
+                extra["exposed_allreduce_ms"] = None if ms_comm is None else round(ms_comm, 4)
+            # per-bucket all-reduce timeline of the last diagnostic step (ms after the backward started), max over
+            # ranks of the exposed tail: shows whether the all-reduce kernels got CUs while the backward ran
+            rep = trainer.comm_report()
+            if rep is not None:
+                ex_t = torch.tensor([rep["exposed_ms"]], dtype=torch.float64, device=dev)
+                if world > 1:
+                    dist.all_reduce(ex_t, op=dist.ReduceOp.MAX)
+                rep["exposed_ms_max_over_ranks"] = round(float(ex_t), 4)
+            extra["allreduce_timeline"] = rep
+        sync_all()
+        from can_distributed_pytorch_amd.parallel.consistency import check_replicas_consistent
+        if a.test_desync and rank == 1:
+            with torch.no_grad():
+                trainer.arena.data[:1].add_(1.0)
+        try:
+            extra["replicas_consistent"] = bool(check_replicas_consistent(trainer.arena.data))
+        except RuntimeError as e:
+            extra["replicas_consistent"] = False
+            print(f"bench.py: {e}", file=sys.stderr)
+    if not cpu:
+        peak = torch.tensor([torch.cuda.max_memory_allocated(dev), torch.cuda.max_memory_reserved(dev)],
+                            device=dev, dtype=torch.float64)
+        if world > 1:
+            dist.all_reduce(peak, op=dist.ReduceOp.MAX)
+        extra["peak_hbm_gb"] = {"allocated": round(float(peak[0]) / 1e9, 3),
+                                "reserved": round(float(peak[1]) / 1e9, 3)}
+    return extra
 
 
 def main(argv=None) -> int:
@@ -264,60 +371,21 @@ def main(argv=None) -> int:
     dt = float(t.item())
     loss = trainer.last_loss()
 
-    # ---- untimed diagnostics
-    extra = {}
-    red = getattr(trainer, "reducer", None)
-    native = a.impl == "hip" and a.dtype != "fp32"       # hip + fp32 = split-bf16 convs under the torch step
-    if native or a.impl == "arena":
-        extra["reducer"] = None if red is None else red.transport
-        if native:
-            extra["rccl_world"] = (red.comm.world if (red is not None and red.comm is not None) else
-                                   (1 if red is None else None))
-            # the all-reduce's CU budget (ncclConfig_t.minCTAs = maxCTAs; 0 = RCCL's default; None: no owned comm)
-            extra["comm_ctas"] = None if red is None else red.comm_ctas
-        extra["buckets_mib"] = None if red is None else [round(b.numel * 4 / 2 ** 20, 3) for b in red.buckets]
-        if a.comm_steps > 0 and not graph_used:
-            trainer.comm_timing = True
-            for i in range(a.comm_steps):
-                trainer.step(*pool[i % len(pool)])
-            trainer.comm_timing = False
-            if native:
-                ms_comm = trainer.exposed_comm_ms()
-                extra["exposed_allreduce_ms"] = None if ms_comm is None else round(ms_comm, 4)
-            # per-bucket all-reduce timeline of the last diagnostic step (ms after the backward started), max over
-            # ranks of the exposed tail: shows whether the all-reduce kernels got CUs while the backward ran
-            rep = trainer.comm_report()
-            if rep is not None:
-                ex_t = torch.tensor([rep["exposed_ms"]], dtype=torch.float64, device=dev)
-                if world > 1:
-                    dist.all_reduce(ex_t, op=dist.ReduceOp.MAX)
-                rep["exposed_ms_max_over_ranks"] = round(float(ex_t), 4)
-            extra["allreduce_timeline"] = rep
-        sync_all()
-        from can_distributed_pytorch_amd.parallel.consistency import check_replicas_consistent
-        if a.test_desync and rank == 1:
-            with torch.no_grad():
-                trainer.arena.data[:1].add_(1.0)
-        try:
-            extra["replicas_consistent"] = bool(check_replicas_consistent(trainer.arena.data))
-        except RuntimeError as e:
-            extra["replicas_consistent"] = False
-            print(f"bench.py: {e}", file=sys.stderr)
-    if not cpu:
-        peak = torch.tensor([torch.cuda.max_memory_allocated(dev), torch.cuda.max_memory_reserved(dev)],
-                            device=dev, dtype=torch.float64)
-        if world > 1:
-            dist.all_reduce(peak, op=dist.ReduceOp.MAX)
-        extra["peak_hbm_gb"] = {"allocated": round(float(peak[0]) / 1e9, 3),
-                                "reserved": round(float(peak[1]) / 1e9, 3)}
+    # ---- what the last timed step handed back, then (--full) the untimed diagnostics
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, train_outputs(trainer, trainer._loss))
+    extra = diagnostics(a, trainer, pool, sync_all, world, rank, dev, cpu, graph_used) if a.full else {}
 
     # self-policing for the driver's N-GPU run: a run whose replicas diverged, or whose own RCCL communicator does
     # not span every rank, is not a valid data-parallel measurement -> non-zero exit on every rank
     problems = []
     if world > 1 and extra.get("replicas_consistent") is False:
         problems.append("replicas diverged (cross-rank weight fingerprints differ)")
-    if world > 1 and "rccl_world" in extra and a.reducer == "rccl" and extra["rccl_world"] != world:
-        problems.append(f"RCCL communicator spans {extra['rccl_world']} rank(s), not {world}")
+    if world > 1 and a.impl == "hip" and a.dtype != "fp32" and a.reducer == "rccl":
+        # (checked in a plain run too: it reads one attribute of the communicator the timed steps used)
+        comm = getattr(getattr(trainer, "reducer", None), "comm", None)
+        if comm is None or comm.world != world:
+            problems.append(f"RCCL communicator spans {None if comm is None else comm.world} rank(s), not {world}")
     bad = torch.tensor([float(len(problems))], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(bad, op=dist.ReduceOp.MAX)

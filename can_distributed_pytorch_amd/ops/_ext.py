@@ -8,7 +8,6 @@ from __future__ import annotations
 
 import importlib
 import os
-import weakref
 
 import torch  # noqa: F401  — must be loaded first: _C resolves libamdhip64/librccl to torch's copies
 
@@ -121,24 +120,21 @@ class launch_on:
 
 
 def own_stream(device) -> "torch.cuda.ExternalStream":
-    """A dedicated non-blocking HIP stream on ``device`` (bindings ``stream_create``), wrapped for torch; destroyed
-    with the wrapper.  torch.cuda.Stream() hands out its pool's 32 streams round-robin, so a long-lived pool stream
-    can alias one another owner takes later (a graph capture's stream)."""
+    """A dedicated non-blocking HIP stream on ``device`` (bindings ``stream_create``), wrapped for torch.
+    torch.cuda.Stream() hands out its pool's 32 streams round-robin, so a long-lived pool stream can alias one
+    another owner takes later (a graph capture's stream).
+
+    The stream lives as long as the process, which releases it at exit.  No finalizer hangs on the wrapper:
+    torch's CUDA stream type inherits torch.Stream's weak-reference slot, but its own deallocator frees the object
+    without clearing the weak references to it.  A ``weakref.finalize`` on the wrapper therefore never ran, and its
+    weak reference kept pointing at the freed wrapper until the interpreter's final garbage collection cleared it
+    through that freed memory: an intermittent segmentation fault at exit, once enough steppers had come and gone
+    for the memory to be reused."""
     C = require()
     dev = torch.device(device)
     with torch.cuda.device(dev):
         ptr = C.stream_create()
-    st = torch.cuda.ExternalStream(ptr, device=dev)
-    weakref.finalize(st, _destroy_stream, C, ptr).atexit = False    # (at exit the process releases it)
-    return st
-
-
-def _destroy_stream(C, ptr):
-    try:
-        torch.cuda.synchronize()
-        C.stream_destroy(ptr)
-    except Exception:          # interpreter shutdown
-        pass
+    return torch.cuda.ExternalStream(ptr, device=dev)
 
 
 def stream_ptr(device=None) -> int:

@@ -52,7 +52,7 @@ def _json_line(stdout: str) -> dict:
 def test_cpu_two_rank_chain_end_to_end():
     """The driver's N-GPU launch path, rehearsed on gloo: bare ``bench.py --gpus 2`` spawns torchrun, each rank runs
     the flat-arena data-parallel step with the bucketed reducer, rank 0 prints ONE max-over-ranks JSON line."""
-    r = _run(["--device", "cpu", "--gpus", "2", "--steps", "2", "--warmup", "1", "--comm-steps", "1"],
+    r = _run(["--device", "cpu", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--comm-steps", "1"],
              {"OMP_NUM_THREADS": "2"})
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     out = _json_line(r.stdout)
@@ -133,9 +133,37 @@ def test_cpu_two_rank_infer():
 def test_cpu_two_rank_forced_desync_exits_nonzero():
     """A run whose replicas diverged is not a valid data-parallel number: the replica fingerprint check fails and the
     bench exits non-zero (the driver's N-GPU run reads the exit status)."""
-    r = _run(["--device", "cpu", "--gpus", "2", "--steps", "1", "--warmup", "0", "--comm-steps", "0",
+    r = _run(["--device", "cpu", "--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--comm-steps", "0",
               "--test-desync"], {"OMP_NUM_THREADS": "2"})
     assert r.returncode != 0, (r.stdout[-2000:], r.stderr[-4000:])
     out = _json_line(r.stdout)
     assert out["replicas_consistent"] is False and out["invalid"]
     assert "INVALID" in r.stderr
+
+
+def test_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run reports the headline line without the --full diagnostics; --dump-outputs writes the last timed
+    step's outputs as float32 / float64 .npy files of at most 64 MB in all, identical from run to run."""
+    import numpy as np
+    outs = []
+    for name in ("a", "b"):
+        r = _run(["--device", "cpu", "--gpus", "1", "--steps", "1", "--warmup", "0", "--dump-outputs",
+                  str(tmp_path / name)], {"OMP_NUM_THREADS": "2"})
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+        outs.append(_json_line(r.stdout))
+    out = outs[0]
+    assert out["steps"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert abs(out["ms_per_step"] * out["value"] - 1000.0 * out["config"]["global_batch"]) < 1.0
+    for key in ("replicas_consistent", "allreduce_timeline", "buckets_mib", "peak_hbm_gb", "exposed_allreduce_ms"):
+        assert key not in out
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"loss.npy", "params.npy", "grads.npy"} <= set(names)
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all()
+        assert np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 * 2 ** 20
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == out["final_loss"]
+    assert np.abs(np.load(tmp_path / "a" / "grads.npy")).max() > 0
