@@ -65,6 +65,12 @@ int can_pack_conv(const float* w, void* fwd, void* dgr, int Co, int Ci, int taps
 int can_pack_multi(const long long* desc, int layers, int max_tiles, int dt, void* stream);
 int can_sgd_pack(const long long* desc, int rows, int max_tiles, long long goff, long long boff, float lr,
                  float momentum, float gscale, float* flags, const float* lr_dev, int dt, void* stream);
+int can_adam(float* p, float* m, float* v, const float* g, size_t n, float lr, double beta1, double beta2, float eps,
+             float wd, int decoupled, float gscale, int step, int* t_dev, float* flags, const float* lr_dev,
+             void* stream);
+int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
+                 long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
+                 int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt, void* stream);
 int can_img_to_nhwc4(const float* img, void* out, int N, int H, int W, int dt, void* stream);
 
 // context.hip

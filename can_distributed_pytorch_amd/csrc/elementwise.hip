@@ -398,25 +398,85 @@ __global__ void __launch_bounds__(256) pack_conv_kernel(const float* __restrict_
 //   {w, fwd, dgr, Co, Ci, taps, first, mode, fwd2, dgr2, si, n}
 // mode 0: a conv weight [Co][Ci][taps] -> fwd [Co][tap][Ci] and dgr [Ci][taps-1-tap][Co] (first: fwd [Co][64],
 // k = tap*4 + c); when fwd2 != 0 the same (1x1 conv{S}_2) weight also goes into the interleaved context packs at
-// scale si (see below).  mode -1 (SGD launches only): a parameter without a pack (bias, head, conv{S}_1), n elements.
+// scale si (see below).  mode -1 (optimizer launches only): a parameter without a pack (bias, head, conv{S}_1), n elements.
 // blockIdx.x = a 32(co) x 32(ci) x taps tile transposed through LDS, so the fp32 reads (ci, tap contiguous per co),
 // the fwd-pack writes (ci contiguous per co, tap) and the dgrad-pack writes (co contiguous per ci, tap) are all
 // coalesced; mode -1: a 4096-element chunk.
 //
-// SGD = true: the optimizer step fused in front of the packing (one launch per step instead of sgd_momentum +
+// OPT != OPT_NONE: the optimizer step fused in front of the packing (one launch per step instead of sgd_momentum +
 // pack_multi: the packs no longer re-read the 83 MB of fp32 masters).  Every arena parameter is exactly one row;
 // grad / momentum live at the same offsets of their own arenas (goff / boff floats from w).  Per element the same
 // fp32 operations as sgd_momentum_kernel (torch.optim.SGD semantics), so the result is bit for bit that of the
 // two-launch step; a skipped step (non-finite loss or gradient) leaves weights, momentum AND packs untouched.
 constexpr int kPackRow = 12;
-struct SgdPackArgs {
-  long long goff, boff;       // gradient / momentum arena offset from the master arena, in floats
+// OPT: which optimizer runs in front of the packing.  OPT_SGD is the step above (weight decay 0); OPT_SGD_WD adds
+// torch.optim.SGD's coupled weight decay (g += wd * p ahead of the momentum); OPT_ADAM is torch.optim.Adam / AdamW
+// (adam1 below), its second moment in a third arena voff floats from the masters.
+enum { OPT_NONE = 0, OPT_SGD = 1, OPT_SGD_WD = 2, OPT_ADAM = 3 };
+struct OptArgs {
+  long long goff, boff, voff;  // gradient / momentum (Adam: first moment) / second-moment arena offsets, in floats
   float lr, momentum, gscale;
+  float wd, eps;
+  int decoupled;               // Adam: 1 = AdamW (p *= 1 - lr*wd), 0 = coupled (g += wd*p)
+  double beta1, beta2;         // double: 1 - float(0.999)^t is 3e-5 off 1 - 0.999^t at t = 1
   float* flags;
   const float* lr_dev;
+  const int* t;                // Adam: applied steps so far, on the device (advanced by opt_tick_kernel); null:
+  int step;                    //   this call's 1-based step from the host instead
 };
-template <int DT, bool SGD>
-__global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __restrict__ desc, SgdPackArgs sa) {
+
+// ---- Adam (torch.optim.Adam / AdamW, no amsgrad, no maximize), fp32 per element:
+//   g' = gscale*g (+ wd*p coupled);  p *= 1 - lr*wd (decoupled);  m += (1-b1)(g' - m);  v = b2*v + (1-b2) g'^2;
+//   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),   bc = 1 - beta^t, t the 1-based step.
+// The per-launch scalars are computed once per thread in double (beta^t by repeated squaring: <= 2*32 multiplies,
+// relative error ~1e-15, so bc1 / bc2 are the float64 values to rounding for any t), as torch computes them on the
+// host.  One function for the fused and the stand-alone kernel: both run the same rounding steps.
+struct AdamCoef { float gscale, cwd, decay, w1, w2, b2, step_size, bc2s, eps; };
+__device__ __forceinline__ double powi(double b, unsigned n) {
+  double r = 1.0;
+  for (; n != 0u; n >>= 1, b *= b)
+    if (n & 1u) r *= b;
+  return r;
+}
+__device__ __forceinline__ AdamCoef adam_coef(const OptArgs& a, float lr) {
+  const int t = (a.t != nullptr) ? a.t[0] + 1 : a.step;
+  const double bc1 = 1.0 - powi(a.beta1, (unsigned)t), bc2 = 1.0 - powi(a.beta2, (unsigned)t);
+  AdamCoef c;
+  c.gscale = a.gscale;
+  c.cwd = a.decoupled ? 0.f : a.wd;
+  c.decay = a.decoupled ? (float)(1.0 - (double)lr * (double)a.wd) : 1.f;
+  c.w1 = (float)(1.0 - a.beta1);
+  c.w2 = (float)(1.0 - a.beta2);
+  c.b2 = (float)a.beta2;
+  c.step_size = (float)((double)lr / bc1);
+  c.bc2s = (float)sqrt(bc2);
+  c.eps = a.eps;
+  return c;
+}
+// (wd = 0: fmaf(0, p, g) = g and p * 1 = p exactly, so one branch-free form serves all three variants; IEEE divide and
+// sqrt: the kernels are bandwidth-bound)
+__device__ __forceinline__ void adam1(const AdamCoef& c, float& p, float& m, float& v, float g) {
+#pragma clang fp contract(off)
+  g = g * c.gscale;
+  g = fmaf(c.cwd, p, g);
+  p = p * c.decay;
+  m = fmaf(c.w1, g - m, m);
+  v = fmaf(c.w2 * g, g, c.b2 * v);
+  const float denom = sqrtf(v) / c.bc2s + c.eps;
+  p = fmaf(-c.step_size, m / denom, p);
+}
+
+// The new optimizers' packs are the 16-bit rounding of the fp32 master as stored: without the barrier the compiler
+// folds the update's last fma into the conversion (v_fma_mixlo_f16: the exact fma result rounded once, to fp16), which
+// differs from a re-pack of the stored master in rare double-rounding cases.  (OPT_NONE / OPT_SGD: code unchanged.)
+template <int OPT>
+__device__ __forceinline__ float as_stored(float x) {
+  if constexpr (OPT >= OPT_SGD_WD) asm volatile("" : "+v"(x));
+  return x;
+}
+
+template <int DT, int OPT>
+__global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __restrict__ desc, OptArgs sa) {
   __shared__ unsigned short t[32][32 * 9 + 2];       // [co][ci*taps + tap] bf16 bits
   const long long* d = desc + (size_t)blockIdx.y * kPackRow;
   float* w = reinterpret_cast<float*>(d[0]);
@@ -425,7 +485,7 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
   const int Co = (int)d[3], Ci = (int)d[4], taps = (int)d[5], first = (int)d[6];
   const int mode = (int)d[7];
   float lr = sa.lr;
-  if constexpr (SGD) {
+  if constexpr (OPT != OPT_NONE) {
     if (sa.flags != nullptr) {
       const bool bad_loss = sa.flags[0] != 0.f;
       if (bad_loss && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) sa.flags[3] = 1.f;
@@ -433,19 +493,34 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
     }
     if (sa.lr_dev != nullptr) lr = sa.lr_dev[0];
   }
+  AdamCoef ac{};                // Adam: filled in below, past the exits of the blocks that have no work
   // one element of the SGD step (sgd_momentum_kernel's order of operations)
   // (explicit multiply / fma: the same rounding steps in both kernels whatever the compiler would contract)
   auto step1 = [&](float* pw, float pv, float gv, float bv) -> float {
-    gv = __fmul_rn(gv, sa.gscale);
-    const float b = fmaf(sa.momentum, bv, gv);
-    pw[sa.boff] = b;
-    const float np = fmaf(-lr, b, pv);
-    pw[0] = np;
-    return np;
+    if constexpr (OPT == OPT_ADAM) {
+      float vv = pw[sa.voff];
+      adam1(ac, pv, bv, vv, gv);
+      pw[sa.boff] = bv;
+      pw[sa.voff] = vv;
+      pw[0] = pv;
+      return pv;
+    } else {
+      gv = __fmul_rn(gv, sa.gscale);
+      if constexpr (OPT == OPT_SGD_WD) gv = fmaf(sa.wd, pv, gv);
+      const float b = fmaf(sa.momentum, bv, gv);
+      pw[sa.boff] = b;
+      const float np = fmaf(-lr, b, pv);
+      pw[0] = np;
+      return np;
+    }
   };
   if (mode < 0) {
-    if constexpr (SGD) {
+    if constexpr (OPT != OPT_NONE) {
       const long long n = d[11];
+      if constexpr (OPT == OPT_ADAM) {
+        if ((long long)blockIdx.x * 4096 >= n) return;
+        ac = adam_coef(sa, lr);
+      }
       const long long e1 = min(n, (long long)(blockIdx.x + 1) * 4096);
       for (long long i = (long long)blockIdx.x * 4096 + threadIdx.x; i < e1; i += 256)
         step1(w + i, w[i], w[i + sa.goff], w[i + sa.boff]);
@@ -454,6 +529,7 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
   }
   const int nci = (Ci + 31) / 32, nco = (Co + 31) / 32;
   if ((int)blockIdx.x >= nci * nco) return;
+  if constexpr (OPT == OPT_ADAM) ac = adam_coef(sa, lr);
   const int co0 = (blockIdx.x / nci) * 32, ci0 = (blockIdx.x % nci) * 32;
   const int cis = min(32, Ci - ci0), cos_ = min(32, Co - co0);
   const int row = cis * taps;                          // contiguous floats per co in the tile
@@ -461,24 +537,71 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
   // per thread (the 2-byte-store form took 81 us per step for the 41 M weights); ragged tiles: element-wise
   const bool v4 = !first && cis == 32 && cos_ == 32 && Ci % 8 == 0 && Co % 8 == 0 && (row & 3) == 0 &&
                   ((((size_t)co0 * Ci + ci0) * taps) & 3) == 0 && (((size_t)Ci * taps) & 3) == 0 &&
-                  ((uintptr_t)w & 15) == 0;
-  if (v4) {
+                  ((uintptr_t)w & 15) == 0 &&
+                  (OPT == OPT_NONE || ((sa.goff | sa.boff | sa.voff) & 3) == 0);   // every arena 16-B aligned
+  if (v4 && OPT == OPT_ADAM) {
+    // Adam: the next iteration's four loads are issued ahead of this one's arithmetic and stores.  The iterations
+    // touch distinct addresses, which the compiler cannot prove (the stores through pw + boff / voff may alias the
+    // loads), so without this each iteration is load - wait - long ALU chain - store with nothing in flight meanwhile.
+    const int r4 = row >> 2, total = 32 * r4;
+    auto at = [&](int i, int& c, int& r) -> float* {
+      c = i / r4;
+      r = (i - c * r4) * 4;
+      return w + ((size_t)(co0 + c) * Ci + ci0) * taps + r;
+    };
+    int i = threadIdx.x, c = 0, r = 0;
+    float* pw = w;
+    float4 v{}, gv{}, m{}, s{};
+    if (i < total) {
+      pw = at(i, c, r);
+      v = *reinterpret_cast<const float4*>(pw);
+      gv = *reinterpret_cast<const float4*>(pw + sa.goff);
+      m = *reinterpret_cast<const float4*>(pw + sa.boff);
+      s = *reinterpret_cast<const float4*>(pw + sa.voff);
+    }
+    while (i < total) {
+      const int in = i + 256;
+      int cn = 0, rn = 0;
+      float* pwn = pw;
+      float4 vn{}, gvn{}, mn{}, sn{};
+      if (in < total) {
+        pwn = at(in, cn, rn);
+        vn = *reinterpret_cast<const float4*>(pwn);
+        gvn = *reinterpret_cast<const float4*>(pwn + sa.goff);
+        mn = *reinterpret_cast<const float4*>(pwn + sa.boff);
+        sn = *reinterpret_cast<const float4*>(pwn + sa.voff);
+      }
+      adam1(ac, v.x, m.x, s.x, gv.x); adam1(ac, v.y, m.y, s.y, gv.y);
+      adam1(ac, v.z, m.z, s.z, gv.z); adam1(ac, v.w, m.w, s.w, gv.w);
+      *reinterpret_cast<float4*>(pw + sa.boff) = m;
+      *reinterpret_cast<float4*>(pw + sa.voff) = s;
+      *reinterpret_cast<float4*>(pw) = v;
+      v.x = as_stored<OPT>(v.x); v.y = as_stored<OPT>(v.y); v.z = as_stored<OPT>(v.z); v.w = as_stored<OPT>(v.w);
+      t[c][r] = f2h<DT>(v.x); t[c][r + 1] = f2h<DT>(v.y); t[c][r + 2] = f2h<DT>(v.z); t[c][r + 3] = f2h<DT>(v.w);
+      i = in; pw = pwn; c = cn; r = rn; v = vn; gv = gvn; m = mn; s = sn;
+    }
+  } else if (v4) {
     const int r4 = row >> 2;
     for (int i = threadIdx.x; i < 32 * r4; i += 256) {
       const int c = i / r4, r = (i - c * r4) * 4;
       float* pw = w + ((size_t)(co0 + c) * Ci + ci0) * taps + r;
       float4 v = *reinterpret_cast<const float4*>(pw);
-      if constexpr (SGD) {
+      if constexpr (OPT != OPT_NONE && OPT != OPT_ADAM) {
         float4 gv = *reinterpret_cast<const float4*>(pw + sa.goff);
         float4 b = *reinterpret_cast<const float4*>(pw + sa.boff);
         gv.x = __fmul_rn(gv.x, sa.gscale); gv.y = __fmul_rn(gv.y, sa.gscale);
         gv.z = __fmul_rn(gv.z, sa.gscale); gv.w = __fmul_rn(gv.w, sa.gscale);
+        if constexpr (OPT == OPT_SGD_WD) {
+          gv.x = fmaf(sa.wd, v.x, gv.x); gv.y = fmaf(sa.wd, v.y, gv.y);
+          gv.z = fmaf(sa.wd, v.z, gv.z); gv.w = fmaf(sa.wd, v.w, gv.w);
+        }
         b.x = fmaf(sa.momentum, b.x, gv.x); b.y = fmaf(sa.momentum, b.y, gv.y);
         b.z = fmaf(sa.momentum, b.z, gv.z); b.w = fmaf(sa.momentum, b.w, gv.w);
         *reinterpret_cast<float4*>(pw + sa.boff) = b;
         v.x = fmaf(-lr, b.x, v.x); v.y = fmaf(-lr, b.y, v.y); v.z = fmaf(-lr, b.z, v.z); v.w = fmaf(-lr, b.w, v.w);
         *reinterpret_cast<float4*>(pw) = v;
       }
+      v.x = as_stored<OPT>(v.x); v.y = as_stored<OPT>(v.y); v.z = as_stored<OPT>(v.z); v.w = as_stored<OPT>(v.w);
       t[c][r] = f2h<DT>(v.x); t[c][r + 1] = f2h<DT>(v.y); t[c][r + 2] = f2h<DT>(v.z); t[c][r + 3] = f2h<DT>(v.w);
     }
   } else {
@@ -486,8 +609,8 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
       const int c = i / row, r = i - c * row;
       float* pw = w + ((size_t)(co0 + c) * Ci + ci0) * taps + r;
       float v = pw[0];
-      if constexpr (SGD) v = step1(pw, v, pw[sa.goff], pw[sa.boff]);
-      t[c][r] = f2h<DT>(v);
+      if constexpr (OPT != OPT_NONE) v = step1(pw, v, pw[sa.goff], pw[sa.boff]);
+      t[c][r] = f2h<DT>(as_stored<OPT>(v));
     }
   }
   __syncthreads();
@@ -564,6 +687,45 @@ __global__ void __launch_bounds__(256) img_to_nhwc4_kernel(const float* __restri
     const float* b = img + n * 3 * HW + p;
     out[i] = make_uint2(pack2<DT>(b[0], b[HW]), pack2<DT>(b[2 * HW], 0.f));
   }
+}
+
+// ---------------------------------------------------------------- Adam (stand-alone) + step count
+// The Adam step over flat buffers, per element exactly the fused kernel's adam1 (so "fused == adam + pack_multi" holds
+// bit for bit); flags / lr_dev as sgd_momentum_kernel.  vec: every pointer 16-B aligned -> float4 groups, the n % 4
+// tail (or, unaligned, everything) element-wise.
+__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                   const float* __restrict__ g, size_t n, int vec, OptArgs a) {
+  if (a.flags != nullptr) {
+    const bool bad_loss = a.flags[0] != 0.f;
+    if (bad_loss && blockIdx.x == 0 && threadIdx.x == 0) a.flags[3] = 1.f;
+    if (bad_loss || a.flags[2] != 0.f) return;
+  }
+  const AdamCoef c = adam_coef(a, (a.lr_dev != nullptr) ? a.lr_dev[0] : a.lr);
+  const size_t n4 = vec ? n / 4 : 0;
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i],
+           vv = reinterpret_cast<float4*>(v)[i];
+    adam1(c, pv.x, mv.x, vv.x, gv.x); adam1(c, pv.y, mv.y, vv.y, gv.y);
+    adam1(c, pv.z, mv.z, vv.z, gv.z); adam1(c, pv.w, mv.w, vv.w, gv.w);
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+    reinterpret_cast<float4*>(p)[i] = pv;
+  }
+  for (size_t i = 4 * n4 + blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    float pv = p[i], mv = m[i], vv = v[i];
+    adam1(c, pv, mv, vv, g[i]);
+    m[i] = mv; v[i] = vv; p[i] = pv;
+  }
+}
+
+// The device step count t advances by one per APPLIED Adam step: a one-thread launch right after the step kernel,
+// which skips on the same flags.  Every block of the step kernel read t before this launch starts (stream order), so
+// all of them saw the same value; a captured step replays both nodes and its bias correction advances.
+__global__ void opt_tick_kernel(const float* __restrict__ flags, int* __restrict__ t) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (flags != nullptr && (flags[0] != 0.f || flags[2] != 0.f)) return;
+  t[0] += 1;
 }
 
 static inline int grid_for(size_t n, int per = 256, int cap = 4096) {
@@ -696,29 +858,79 @@ extern "C" int can_img_to_nhwc4(const float* img, void* out, int N, int H, int W
 extern "C" int can_pack_multi(const long long* desc, int layers, int max_tiles, int dt, void* stream) {
   if (layers <= 0) return 0;
   // grid.x covers the largest layer's 32x32 tiles (B1: 512 -> 1024 channels = 512 tiles)
-  SgdPackArgs sa{};
+  OptArgs sa{};
   hipStream_t s = (hipStream_t)stream;
   if (dt == DT_F16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_F16, false>), dim3(max_tiles, layers), dim3(256), 0, s, desc, sa);
+    hipLaunchKernelGGL((pack_multi_kernel<DT_F16, OPT_NONE>), dim3(max_tiles, layers), dim3(256), 0, s, desc, sa);
   else if (dt == DT_BF16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, false>), dim3(max_tiles, layers), dim3(256), 0, s, desc, sa);
+    hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, OPT_NONE>), dim3(max_tiles, layers), dim3(256), 0, s, desc, sa);
   else
     return -20;
   return (int)hipGetLastError();
 }
 
-// The fused optimizer step (pack_multi_kernel<DT, true>): rows cover every parameter of the arena once; grad and
+// The fused optimizer step (pack_multi_kernel<DT, OPT_SGD>): rows cover every parameter of the arena once; grad and
 // momentum arenas are at goff / boff floats from the master arena.
 extern "C" int can_sgd_pack(const long long* desc, int rows, int max_tiles, long long goff, long long boff, float lr,
                             float momentum, float gscale, float* flags, const float* lr_dev, int dt, void* stream) {
   if (rows <= 0) return 0;
-  SgdPackArgs sa{goff, boff, lr, momentum, gscale, flags, lr_dev};
+  OptArgs sa{};
+  sa.goff = goff; sa.boff = boff; sa.lr = lr; sa.momentum = momentum; sa.gscale = gscale;
+  sa.flags = flags; sa.lr_dev = lr_dev;
   hipStream_t s = (hipStream_t)stream;
   if (dt == DT_F16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_F16, true>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
+    hipLaunchKernelGGL((pack_multi_kernel<DT_F16, OPT_SGD>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
   else if (dt == DT_BF16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, true>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
+    hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, OPT_SGD>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
   else
     return -20;
+  return (int)hipGetLastError();
+}
+
+// Stand-alone Adam / AdamW over flat fp32 buffers (any n, any alignment).  t_dev: the device step count (applied steps
+// so far; advanced by one here unless the step is skipped through flags); null: `step` is this call's 1-based step.
+extern "C" int can_adam(float* p, float* m, float* v, const float* g, size_t n, float lr, double beta1, double beta2,
+                        float eps, float wd, int decoupled, float gscale, int step, int* t_dev, float* flags,
+                        const float* lr_dev, void* stream) {
+  if (n == 0) return 0;
+  if (t_dev == nullptr && step < 1) return -2;
+  OptArgs a{};
+  a.lr = lr; a.gscale = gscale; a.wd = wd; a.eps = eps; a.decoupled = decoupled; a.beta1 = beta1; a.beta2 = beta2;
+  a.flags = flags; a.lr_dev = lr_dev; a.t = t_dev; a.step = step;
+  const int vec = (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) & 15) == 0;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(vec ? (n + 3) / 4 : n, 256, 4096)), dim3(256), 0, s, p, m, v, g, n, vec,
+                     a);
+  if (t_dev != nullptr) hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t_dev);
+  return (int)hipGetLastError();
+}
+
+// The fused optimizer step for every optimizer: opt 1 = SGD-momentum (can_sgd_pack's kernel), 2 = SGD with coupled
+// weight decay, 3 = Adam / AdamW (mom = first moment, second moment at voff; t_dev required, advanced when applied).
+extern "C" int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
+                            long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
+                            int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt,
+                            void* stream) {
+  if (rows <= 0) return 0;
+  if (opt < OPT_SGD || opt > OPT_ADAM || (opt == OPT_ADAM && t_dev == nullptr)) return -2;
+  if (dt != DT_F16 && dt != DT_BF16) return -20;
+  OptArgs sa{};
+  sa.goff = goff; sa.boff = boff; sa.voff = (opt == OPT_ADAM) ? voff : 0;
+  sa.lr = lr; sa.momentum = momentum; sa.gscale = gscale; sa.wd = wd; sa.eps = eps; sa.decoupled = decoupled;
+  sa.beta1 = beta1; sa.beta2 = beta2; sa.flags = flags; sa.lr_dev = lr_dev; sa.t = t_dev;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(max_tiles, rows), blk(256);
+#define CAN_OPT_LAUNCH(O)                                                                                       \
+  do {                                                                                                           \
+    if (dt == DT_F16) hipLaunchKernelGGL((pack_multi_kernel<DT_F16, O>), grid, blk, 0, s, desc, sa);             \
+    else hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, O>), grid, blk, 0, s, desc, sa);                          \
+  } while (0)
+  if (opt == OPT_SGD) CAN_OPT_LAUNCH(OPT_SGD);
+  else if (opt == OPT_SGD_WD) CAN_OPT_LAUNCH(OPT_SGD_WD);
+  else {
+    CAN_OPT_LAUNCH(OPT_ADAM);
+    hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t_dev);
+  }
+#undef CAN_OPT_LAUNCH
   return (int)hipGetLastError();
 }

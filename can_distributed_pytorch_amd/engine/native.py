@@ -149,11 +149,17 @@ class SplitCapture:
             pass
 
 
+OPTIMIZERS = ("sgd", "adam", "adamw")
+
+
 class NativeStepper:
     def __init__(self, device, dtype="bf16", world=1, lr=1e-7, momentum=0.95, batch=8, height=768, width=1024,
                  graph=True, model: Optional[CANNet] = None, reducer=None, bucket_mb: float = 25.0,
                  reducer_transport: Optional[str] = None, init_scale="auto", scale_interval: int = 2000,
-                 graph_max_shapes: int = 8, comm_ctas: Optional[int] = None, graph_bind_inputs: bool = False):
+                 graph_max_shapes: int = 8, comm_ctas: Optional[int] = None, graph_bind_inputs: bool = False,
+                 optimizer: str = "sgd", weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         if dtype not in ACT_DTYPES:
             raise ValueError(f"the native step computes in bf16 or fp16 (fp32 master weights), got {dtype!r}; "
                              "use --impl torch for fp32")
@@ -166,14 +172,22 @@ class NativeStepper:
         self.model.exec_backend = "hip"
         self.world = world
         self.momentum = momentum
+        self.optimizer = optimizer
+        self.weight_decay = float(weight_decay)
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
         self.params = list(self.model.parameters())
         self.ex = CANNetExecutor(self.model, dtype=ACT_DTYPES[dtype])
         self.model._executor = self.ex
         # fp32 master/grad arenas laid out in gradient-ready order (contiguous buckets)
         self.arena = FlatArena(self.params, self.device, order=self.ex.grad_ready_order())
         self.mom = torch.zeros_like(self.arena.data)  # momentum buffer (zero init == torch's first-step clone)
+        # Adam / AdamW: self.mom is the first moment; the second moment and the device count of applied steps (the
+        # kernel's bias correction reads it, so a captured step advances it on replay) exist only for them
+        self.mom2 = torch.zeros_like(self.arena.data) if optimizer != "sgd" else None
+        self.opt_t = torch.zeros(1, dtype=torch.int32, device=self.device) if optimizer != "sgd" else None
         self.grads = self.arena.grad_views()
-        self.ex.sgd_prepare(self.arena.data, self.arena.grad, self.mom)   # (device descriptor: before any capture)
+        self.ex.opt_prepare(self.arena.data, self.arena.grad, self.mom, self.mom2)   # (device descriptor: before any capture)
         # [non-finite loss (any rank after the all-reduce), loss, non-finite gradient (fp16), sticky non-finite]
         self.flags = torch.zeros(4, dtype=torch.float32, device=self.device)
         self._lr_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -298,9 +312,15 @@ class NativeStepper:
         if not update:
             return self.flags[1:2]
         with trace_range("cannet/sgd"):
-            # SGD over the arena and the 16-bit weight packs in ONE launch (executor.sgd_step)
-            ex.sgd_step(self.arena.data, self.arena.grad, self.mom, self._lr, self.momentum, 1.0 / self.world,
-                        flags=self.flags, lr_dev=self._lr_dev)
+            # the optimizer over the arena and the 16-bit weight packs in ONE launch (executor.sgd_step / opt_step)
+            if self.optimizer == "sgd" and self.weight_decay == 0:
+                ex.sgd_step(self.arena.data, self.arena.grad, self.mom, self._lr, self.momentum, 1.0 / self.world,
+                            flags=self.flags, lr_dev=self._lr_dev)
+            else:
+                ex.opt_step(self.arena.data, self.arena.grad, self.mom, self._lr, 1.0 / self.world,
+                            optimizer=self.optimizer, momentum=self.momentum, weight_decay=self.weight_decay,
+                            betas=self.betas, eps=self.eps, mom2=self.mom2, step=self.opt_t, flags=self.flags,
+                            lr_dev=self._lr_dev)
             if sc is not None:
                 self.C.scale_update(self.flags.data_ptr() + 8, sc.data_ptr(), int(self.scale_interval), 2.0, 0.5,
                                     float(2 ** 24), st)
@@ -492,7 +512,10 @@ class NativeStepper:
 
     def resume_state(self) -> dict:
         """Device state a resumed run needs besides weights and momentum (checkpoint.save_train_state)."""
-        st = {"lr": self._lr, "steps": self.steps}
+        st = {"lr": self._lr, "steps": self.steps, "optimizer": self.optimizer, "momentum": float(self.momentum),
+              "weight_decay": self.weight_decay, "beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps}
+        if self.opt_t is not None:
+            st["opt_steps"] = int(self.opt_t.item())
         if self.scaler is not None:
             st["scaler"] = self.scaler
         return st
@@ -500,6 +523,12 @@ class NativeStepper:
     def load_resume_state(self, st: Optional[dict]):
         if not st:
             return
+        saved = st.get("optimizer", "sgd")             # (a state from before the optimizer choice: SGD)
+        if saved != self.optimizer:
+            raise ValueError(f"the saved state is a {saved!r} run, this stepper runs {self.optimizer!r}: their "
+                             "optimizer states are not interchangeable")
+        if self.opt_t is not None:
+            self.opt_t.fill_(int(st.get("opt_steps", 0)))
         self.lr = float(st.get("lr", self._lr))
         self.steps = int(st.get("steps", self.steps))
         if self.scaler is not None and st.get("scaler") is not None:

@@ -1,7 +1,7 @@
 """Training-step engines shared by train.py and bench.py.
 
 Two implementations of ONE training step (zero_grad -> forward -> MSE(sum)
--> backward + gradient all-reduce -> SGD(momentum 0.95)), the reference's
+-> backward + gradient all-reduce -> optimizer: SGD(momentum 0.95) by default, Adam / AdamW), the reference's
 step (utils/train_eval_utils.py:28-52):
 
 * ``TorchStepper`` — the stock PyTorch-ROCm reference stack: nn.Conv2d
@@ -23,11 +23,26 @@ import torch.distributed as dist
 from ..models.cannet import CANNet
 
 
+OPTIMIZERS = ("sgd", "adam", "adamw")
+
+
+def make_torch_optimizer(params, optimizer="sgd", lr=1e-7, momentum=0.95, weight_decay=0.0, betas=(0.9, 0.999),
+                         eps=1e-8):
+    """torch.optim.SGD / Adam / AdamW from the steppers' common optimizer arguments."""
+    if optimizer == "sgd":
+        return torch.optim.SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
+    if optimizer == "adam":
+        return torch.optim.Adam(params, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+    if optimizer == "adamw":
+        return torch.optim.AdamW(params, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+    raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+
+
 class TorchStepper:
     exec_backend = "torch"
 
     def __init__(self, device, dtype="fp32", world=1, lr=1e-7, momentum=0.95, channels_last=None, model=None,
-                 bucket_mb: float = 25.0):
+                 bucket_mb: float = 25.0, optimizer="sgd", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
         self.device = torch.device(device)
         self.model = (model or CANNet(backend=self.exec_backend)).to(self.device)
         self.model.exec_backend = self.exec_backend
@@ -40,8 +55,10 @@ class TorchStepper:
             dev_ids = [self.device.index] if self.device.type == "cuda" else None
             self.net = torch.nn.parallel.DistributedDataParallel(self.model, device_ids=dev_ids,
                                                                  bucket_cap_mb=bucket_mb)
-        self.opt = torch.optim.SGD([p for p in self.model.parameters() if p.requires_grad],
-                                   lr=lr * world, momentum=momentum, weight_decay=0)
+        self.optimizer = optimizer
+        self.opt = make_torch_optimizer([p for p in self.model.parameters() if p.requires_grad], optimizer,
+                                        lr=lr * world, momentum=momentum, weight_decay=weight_decay, betas=betas,
+                                        eps=eps)
         self.crit = torch.nn.MSELoss(reduction="sum")
         self._loss = None
         self.autocast = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(dtype)
@@ -96,8 +113,15 @@ class ArenaStepper:
     non-finite loss on every rank alike, and the init-time parameter sync as one broadcast of the arena."""
     exec_backend = "torch"
 
-    def __init__(self, device="cpu", world=1, lr=1e-7, momentum=0.95, model=None, bucket_mb: float = 25.0):
+    def __init__(self, device="cpu", world=1, lr=1e-7, momentum=0.95, model=None, bucket_mb: float = 25.0,
+                 optimizer="sgd", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
         from ..models.cannet import grad_ready_order
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+        self.optimizer = optimizer
+        self.weight_decay = float(weight_decay)
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
         from ..parallel.reducer import BucketedReducer
         from ..utils.flat import FlatArena
         self.device = torch.device(device)
@@ -109,7 +133,9 @@ class ArenaStepper:
         self.params = list(self.model.parameters())
         order = grad_ready_order(self.model)
         self.arena = FlatArena(self.params, self.device, order=order)
-        self.mom = torch.zeros_like(self.arena.data)
+        self.mom = torch.zeros_like(self.arena.data)          # SGD momentum / Adam first moment
+        self.mom2 = torch.zeros_like(self.arena.data) if optimizer != "sgd" else None
+        self.opt_steps = 0                                    # applied Adam steps (the bias correction's t)
         self.reducer = BucketedReducer(self.arena, order, bucket_mb=bucket_mb, transport="torch")
         self.reducer.attach_hooks()
         self.flags = torch.zeros(2, dtype=torch.float32, device=self.device)
@@ -137,11 +163,35 @@ class ArenaStepper:
             self.flags[1] = loss.detach()
             red.allreduce_scalars(self.flags)
             if self.flags[0] == 0:
-                # buf = m * buf + g / W ; p -= lr * buf   (torch.optim.SGD semantics, zero-initialised buffer)
-                self.mom.mul_(self.momentum).add_(self.arena.grad, alpha=1.0 / self.world)
-                self.arena.data.add_(self.mom, alpha=-self.lr)
+                self._update()
         self._loss = self.flags[1:2] / self.world
         return self._loss
+
+    def _update(self):
+        """The native step's three optimizers (elementwise.hip) in torch ops over the arena."""
+        p, g, wd = self.arena.data, self.arena.grad, self.weight_decay
+        if self.optimizer == "sgd":
+            # buf = m * buf + g / W (+ wd * p) ; p -= lr * buf   (torch.optim.SGD semantics, zero-initialised buffer)
+            if wd != 0:
+                g = (g * (1.0 / self.world)).add_(p, alpha=wd)
+                self.mom.mul_(self.momentum).add_(g)
+            else:
+                self.mom.mul_(self.momentum).add_(g, alpha=1.0 / self.world)
+            p.add_(self.mom, alpha=-self.lr)
+            return
+        # torch.optim.Adam / AdamW (no amsgrad), in torch's order of operations
+        b1, b2 = self.betas
+        g = g * (1.0 / self.world)
+        if self.optimizer == "adamw":
+            p.mul_(1.0 - self.lr * wd)
+        elif wd != 0:
+            g = g.add(p, alpha=wd)
+        self.opt_steps += 1
+        t = self.opt_steps
+        self.mom.lerp_(g, 1.0 - b1)
+        self.mom2.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+        denom = (self.mom2.sqrt() / (1.0 - b2 ** t) ** 0.5).add_(self.eps)
+        p.addcdiv_(self.mom, denom, value=-self.lr / (1.0 - b1 ** t))
 
     def comm_report(self, reset: bool = True) -> Optional[dict]:
         """The last timed step's per-bucket all-reduce report (BucketedReducer.timings)."""
@@ -157,15 +207,17 @@ class ArenaStepper:
 def build_trainer(impl="hip", dtype="bf16", device="cuda", world=1, lr=1e-7, batch=8,
                   height=768, width=1024, graph=True, model=None, bucket_mb: float = 25.0,
                   reducer_transport: Optional[str] = None, comm_ctas: Optional[int] = None,
-                  graph_bind_inputs: bool = False, graph_max_shapes: int = 8):
+                  graph_bind_inputs: bool = False, graph_max_shapes: int = 8, optimizer: str = "sgd",
+                  momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
+    opt = dict(optimizer=optimizer, momentum=momentum, weight_decay=weight_decay, betas=betas, eps=eps)
     if impl == "arena":
-        return ArenaStepper(device, world=world, lr=lr, model=model, bucket_mb=bucket_mb)
+        return ArenaStepper(device, world=world, lr=lr, model=model, bucket_mb=bucket_mb, **opt)
     if impl == "torch":
-        return TorchStepper(device, dtype=dtype, world=world, lr=lr, model=model, bucket_mb=bucket_mb)
+        return TorchStepper(device, dtype=dtype, world=world, lr=lr, model=model, bucket_mb=bucket_mb, **opt)
     if dtype == "fp32":
-        return Fp32Stepper(device, world=world, lr=lr, model=model, bucket_mb=bucket_mb)
+        return Fp32Stepper(device, world=world, lr=lr, model=model, bucket_mb=bucket_mb, **opt)
     from .native import NativeStepper
     return NativeStepper(device, dtype=dtype, world=world, lr=lr, batch=batch, height=height,
                          width=width, graph=graph, model=model, bucket_mb=bucket_mb,
                          reducer_transport=reducer_transport, comm_ctas=comm_ctas,
-                         graph_bind_inputs=graph_bind_inputs, graph_max_shapes=graph_max_shapes)
+                         graph_bind_inputs=graph_bind_inputs, graph_max_shapes=graph_max_shapes, **opt)

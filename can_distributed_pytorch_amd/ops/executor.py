@@ -236,6 +236,45 @@ class CANNetExecutor(ContextSchedule):
         return (self._sgd_desc.data_ptr(), self._sgd_desc.shape[0], self._sgd_tiles,
                 (grad.data_ptr() - base) // esz, (mom.data_ptr() - base) // esz)
 
+    def opt_step(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor, lr: float, gscale: float,
+                 optimizer: str = "sgd", momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999),
+                 eps: float = 1e-8, mom2: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None,
+                 flags: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None):
+        """The fused optimizer step for every optimizer (elementwise.hip pack_multi_kernel<DT, OPT>), ONE launch over
+        the arena that also writes the 16-bit packs, as ``sgd_step``: ``optimizer`` = "sgd" (torch.optim.SGD with
+        momentum and coupled ``weight_decay``; weight decay 0 runs sgd_step's kernel), "adam" (torch.optim.Adam,
+        coupled weight decay) or "adamw" (decoupled).  Adam: ``mom`` / ``mom2`` are the first / second moment arenas
+        and ``step`` the int32 device count of applied steps, which a one-thread launch after the step advances
+        unless the step was skipped through ``flags``."""
+        desc, rows, tiles, goff, boff, voff = self.opt_prepare(data, grad, mom, mom2)
+        if optimizer not in ("sgd", "adam", "adamw"):
+            raise ValueError(f"opt_step: unknown optimizer {optimizer!r}")
+        adam = optimizer != "sgd"
+        if adam:
+            if mom2 is None or step is None:
+                raise ValueError("opt_step: Adam needs the second-moment arena and the device step count")
+            if step.dtype != torch.int32 or step.device != data.device or step.numel() < 1:
+                raise ValueError("opt_step: step must be an int32 tensor on the arena's device")
+        kind = 3 if adam else (2 if weight_decay != 0 else 1)
+        self.C.opt_pack(desc, rows, tiles, kind, goff, boff, voff, float(lr), float(momentum), float(betas[0]),
+                        float(betas[1]), float(eps), float(weight_decay), int(optimizer == "adamw"), float(gscale),
+                        step.data_ptr() if adam else 0, flags.data_ptr() if flags is not None else 0,
+                        lr_dev.data_ptr() if lr_dev is not None else 0, self.dt, self._stream())
+        self._pack_version = self._weights_version()
+
+    def opt_prepare(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor,
+                    mom2: Optional[torch.Tensor] = None):
+        """sgd_prepare (the descriptor rows are shared) + the second-moment arena's offset (0 without one)."""
+        desc, rows, tiles, goff, boff = self.sgd_prepare(data, grad, mom)
+        voff = 0
+        if mom2 is not None:
+            if mom2.shape != data.shape or mom2.dtype != torch.float32 or mom2.device != data.device:
+                raise ValueError("opt_step: the second-moment arena must match the parameter arena")
+            if (mom2.data_ptr() - data.data_ptr()) % data.element_size():
+                raise ValueError("opt_step: arena offsets must be whole floats")
+            voff = (mom2.data_ptr() - data.data_ptr()) // data.element_size()
+        return desc, rows, tiles, goff, boff, voff
+
     def mark_weights_updated(self):
         """Called by the fused optimizer after it has re-packed (keeps versions in sync)."""
         self._pack_version = self._weights_version()

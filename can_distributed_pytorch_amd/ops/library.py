@@ -21,6 +21,11 @@ GPU — and an autograd formula built from the native backward kernels.
   cannet::sgd_momentum_(param, momentum_buf, grad, lr, momentum, grad_scale) -> ()
       in-place fused SGD with momentum on contiguous fp32 tensors (torch.optim.SGD semantics, weight decay 0,
       dampening 0: buf = momentum * buf + grad_scale * grad; param -= lr * buf), one kernel.
+  cannet::adam_(param, exp_avg, exp_avg_sq, grad, step, lr, beta1, beta2, eps, weight_decay, decoupled,
+                grad_scale) -> ()
+      in-place fused Adam (decoupled=False: torch.optim.Adam, weight decay added to the gradient) or AdamW
+      (decoupled=True) on contiguous fp32 tensors, one kernel; ``step`` is the 1-based step of this call (the bias
+      corrections are 1 - beta^step); no amsgrad, no maximize.
 
 ``Conv2dNHWC`` / ``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master parameters.
 """
@@ -184,6 +189,50 @@ def sgd_momentum_(param: torch.Tensor, momentum_buf: torch.Tensor, grad: torch.T
 
 @sgd_momentum_.register_fake
 def _(param, momentum_buf, grad, lr, momentum, grad_scale=1.0):
+    return None
+
+
+def _adam_aten(param, exp_avg, exp_avg_sq, grad, step, lr, beta1, beta2, eps, weight_decay, decoupled, grad_scale):
+    """torch.optim.Adam / AdamW's single-tensor update in ATen ops (the fallback for tensors off 16-byte alignment)."""
+    g = grad * grad_scale
+    if decoupled:
+        param.mul_(1.0 - lr * weight_decay)
+    elif weight_decay != 0:
+        g = g.add(param, alpha=weight_decay)
+    exp_avg.lerp_(g, 1.0 - beta1)
+    exp_avg_sq.mul_(beta2).addcmul_(g, g, value=1.0 - beta2)
+    denom = (exp_avg_sq.sqrt() / (1.0 - beta2 ** step) ** 0.5).add_(eps)
+    param.addcdiv_(exp_avg, denom, value=-lr / (1.0 - beta1 ** step))
+
+
+@torch.library.custom_op(f"{_LIB}::adam_", mutates_args=("param", "exp_avg", "exp_avg_sq"))
+def adam_(param: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, grad: torch.Tensor, step: int,
+          lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
+          decoupled: bool = False, grad_scale: float = 1.0) -> None:
+    ts = ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (grad, "grad"))
+    for t, name in ts:
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{name} must be a contiguous fp32 GPU tensor")
+    if not (param.numel() == exp_avg.numel() == exp_avg_sq.numel() == grad.numel()):
+        raise ValueError("param / exp_avg / exp_avg_sq / grad sizes differ")
+    if step < 1:
+        raise ValueError("step is the 1-based step of this call")
+    n = param.numel()
+    if n == 0:
+        return
+    hp = (step, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), bool(decoupled),
+          float(grad_scale))
+    if any(t.data_ptr() % 16 for t, _ in ts):
+        _adam_aten(param, exp_avg, exp_avg_sq, grad, *hp)            # as sgd_momentum_: float4 groups need 16 B
+        return
+    # adam_kernel takes the n % 4 tail itself, so the op is C.adam bit for bit
+    _ext.require().adam(param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.data_ptr(), n, hp[1], hp[2],
+                        hp[3], hp[4], hp[5], int(hp[6]), hp[7], int(step), 0, 0, 0, _ext.stream_ptr(param.device))
+
+
+@adam_.register_fake
+def _(param, exp_avg, exp_avg_sq, grad, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+      decoupled=False, grad_scale=1.0):
     return None
 
 

@@ -6,7 +6,7 @@
   (the reference's strict=False load of its own DDP checkpoint silently loads
   nothing).  Loading uses ``weights_only=True``: nothing in the file executes.
 * ``save_train_state`` / ``load_train_state``: exact resume (weights, SGD
-  momentum — native arena or torch optimizer state —, epoch, min_mae,
+  momentum or Adam moments — native arenas or torch optimizer state —, epoch, min_mae,
   min_epoch, the native stepper's loss scale / lr / step count, and the
   torch CPU+CUDA, numpy and Python RNG streams) — the reference has none.
 """
@@ -74,15 +74,20 @@ def _set_rng_state(st: dict) -> None:
 
 def save_train_state(path: str, model, momentum: Optional[torch.Tensor], epoch: int, min_mae: float,
                      extra: Optional[dict] = None, optimizer=None, min_epoch: int = 0,
-                     stepper_state: Optional[dict] = None) -> None:
+                     stepper_state: Optional[dict] = None, momentum2: Optional[torch.Tensor] = None,
+                     optimizer_name: Optional[str] = None) -> None:
     """Everything an uninterrupted run carries into the next epoch: weights, the momentum (native arena, or
     the torch optimizer's state_dict), epoch / min_mae / min_epoch, the native stepper's device state (fp16 loss
     scale, lr, step count) and every RNG stream.  The data order needs no state: DistributedSampler is a
-    function of (seed, epoch) and the flip of CrowdDataset one of (seed, epoch, index)."""
+    function of (seed, epoch) and the flip of CrowdDataset one of (seed, epoch, index).  Adam / AdamW on the native
+    arena: ``momentum`` is the first moment, ``momentum2`` the second; ``optimizer_name`` ("sgd" / "adam" / "adamw")
+    is checked on load."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     state = {
         "model": {k: v.detach().cpu() for k, v in _unwrap(model).state_dict().items()},
         "momentum": None if momentum is None else momentum.detach().cpu(),
+        "momentum2": None if momentum2 is None else momentum2.detach().cpu(),
+        "optimizer_name": optimizer_name,
         "optimizer": None if optimizer is None else optimizer.state_dict(),
         "stepper": None if stepper_state is None else {k: (v.detach().cpu() if torch.is_tensor(v) else v)
                                                        for k, v in stepper_state.items()},
@@ -99,13 +104,23 @@ def save_train_state(path: str, model, momentum: Optional[torch.Tensor], epoch: 
 
 
 def load_train_state(path: str, model, momentum: Optional[torch.Tensor] = None, optimizer=None,
-                     restore_rng: bool = True) -> dict:
+                     restore_rng: bool = True, momentum2: Optional[torch.Tensor] = None,
+                     optimizer_name: Optional[str] = None) -> dict:
     """Restores what save_train_state wrote (weights_only load: nothing in the file executes).  Returns
-    {"epoch", "min_mae", "min_epoch", "stepper"}."""
+    {"epoch", "min_mae", "min_epoch", "stepper"}.  ``optimizer_name``: the optimizer of the resuming run; a state
+    written by another one (a state without the key is an SGD state) raises instead of reusing its buffers."""
     st = torch.load(path, map_location="cpu", weights_only=True)
+    saved = st.get("optimizer_name") or ("sgd" if st.get("momentum2") is None else "adam")
+    if optimizer_name is not None and saved != optimizer_name:
+        raise ValueError(f"{path} holds the optimizer state of a {saved!r} run and cannot resume a "
+                         f"{optimizer_name!r} run: restart without --resume, or pass --optimizer {saved}")
+    if momentum2 is not None and st.get("momentum2") is None:
+        raise ValueError(f"{path} has no second-moment arena to resume {optimizer_name or 'Adam'} from")
     load_checkpoint_dict(model, st["model"])
     if momentum is not None and st.get("momentum") is not None:
         momentum.copy_(st["momentum"].to(momentum.device))
+    if momentum2 is not None:
+        momentum2.copy_(st["momentum2"].to(momentum2.device))
     if optimizer is not None and st.get("optimizer") is not None:
         optimizer.load_state_dict(st["optimizer"])
     if restore_rng and st.get("rng") is not None:

@@ -57,6 +57,16 @@ def build_parser():
     p.add_argument("--epochs", type=int, default=500)
     p.add_argument("--batch-size", type=int, default=1)
     p.add_argument("--lr", type=float, default=1e-7)
+    p.add_argument("--optimizer", choices=["sgd", "adam", "adamw"], default="sgd",
+                   help="sgd: torch.optim.SGD semantics (the reference); adam / adamw: torch.optim.Adam / AdamW "
+                        "(coupled / decoupled --weight-decay).  Every optimizer runs as one fused native kernel with "
+                        "--impl hip and as the torch.optim one with --impl torch; --lr is multiplied by the world "
+                        "size for every optimizer (the reference's rule)")
+    p.add_argument("--momentum", type=float, default=0.95, help="SGD momentum")
+    p.add_argument("--weight-decay", type=float, default=0.0)
+    p.add_argument("--beta1", type=float, default=0.9, help="Adam / AdamW first-moment decay")
+    p.add_argument("--beta2", type=float, default=0.999, help="Adam / AdamW second-moment decay")
+    p.add_argument("--eps", type=float, default=1e-8, help="Adam / AdamW epsilon")
     p.add_argument("--lrf", type=float, default=0.1, help="final lr factor for --lr-schedule cosine (unused otherwise, as in the reference)")
     p.add_argument("--syncBN", type=str2bool, default=True,
                    help="convert BatchNorm to SyncBatchNorm when world > 1 (the reference model has no BN: a no-op "
@@ -185,27 +195,30 @@ def main(args):
     # the fused native stepper (flat arena, RCCL reducer, device lr) runs --impl hip in bf16 / fp16; every other
     # combination (--impl torch, and --impl hip --dtype fp32 = Fp32Stepper) is a TorchStepper with a torch optimizer
     native = args.impl == "hip" and args.dtype != "fp32"
+    opt = dict(optimizer=args.optimizer, momentum=args.momentum, weight_decay=args.weight_decay,
+               betas=(args.beta1, args.beta2), eps=args.eps)
     if native:
         stepper = build_trainer(impl="hip", dtype=args.dtype, device=device, world=world, lr=base_lr, graph=graph,
                                 model=model, bucket_mb=args.bucket_mb, comm_ctas=args.comm_ctas,
-                                graph_max_shapes=args.graph_cache)
+                                graph_max_shapes=args.graph_cache, **opt)
         net = stepper.model
-        momentum = stepper.mom
+        momentum, momentum2 = stepper.mom, stepper.mom2
     else:
         # --impl torch: stock ATen / MIOpen; --impl hip --dtype fp32: split-bf16 convolutions on the native
         # MFMA kernels (engine/trainer.Fp32Stepper), the rest of the step as the torch one
         stepper = build_trainer(impl=args.impl, dtype=args.dtype if use_gpu else "fp32", device=device, world=world,
-                                lr=base_lr, model=model, bucket_mb=args.bucket_mb)
+                                lr=base_lr, model=model, bucket_mb=args.bucket_mb, **opt)
         if world > 1:
             for p in stepper.model.parameters():
                 dist.broadcast(p.data, src=0)
         net = stepper.net
-        momentum = None
+        momentum = momentum2 = None
 
     start_epoch, min_mae, min_epoch = 0, float("inf"), 0
     if args.resume and os.path.exists(args.resume):
         rs = load_train_state(args.resume, stepper.model, momentum,
-                              optimizer=None if native else stepper.opt)
+                              optimizer=None if native else stepper.opt, momentum2=momentum2,
+                              optimizer_name=args.optimizer)
         start_epoch, min_mae, min_epoch = rs["epoch"] + 1, rs["min_mae"], rs["min_epoch"]
         if native:
             stepper.load_resume_state(rs["stepper"])
@@ -247,7 +260,8 @@ def main(args):
                 save_checkpoint(stepper.model, os.path.join(args.checkpoint_dir, f"epoch_{epoch}.pth"))
             save_train_state(os.path.join(args.checkpoint_dir, "last_state.pth"), stepper.model, momentum, epoch,
                              min_mae, optimizer=None if native else stepper.opt, min_epoch=min_epoch,
-                             stepper_state=stepper.resume_state() if native else None)
+                             stepper_state=stepper.resume_state() if native else None, momentum2=momentum2,
+                             optimizer_name=args.optimizer)
             lr_now = stepper.lr if native else stepper.opt.param_groups[0]["lr"]
             ips = len(train_loader) * args.batch_size * world / max(t_train, 1e-9)
             print(f"[epoch {epoch}] loss: {mean_loss:.4f} mae: {mean_mae:.3f}, min_mae: {min_mae:.3f}, "
