@@ -56,7 +56,7 @@ int can_head_train(const void* y, const float* w, const float* b, const float* g
                    int nblk, float* dw, float* db, float* loss, int P, float gscale, float beta, const float* lscale,
                    float* nonfinite, int dt, void* stream, int pitch, int wv);
 int can_sgd_momentum(float* p, float* buf, const float* g, size_t n, float lr, float momentum, float gscale,
-                     int first, float* flags, const float* lr_dev, void* stream);
+                     int first, float* flags, const float* lr_dev, void* stream, const float* gmul);
 int can_grad_nonfinite(const float* g, size_t n, float* flags, void* stream);
 int can_split_x3(const float* src, void* dst, long long M, int C, int stride, int mode, int pattern, void* stream);
 int can_scale_update(const float* flags, float* scaler, int interval, float growth, float backoff, float max_scale,
@@ -67,10 +67,16 @@ int can_sgd_pack(const long long* desc, int rows, int max_tiles, long long goff,
                  float momentum, float gscale, float* flags, const float* lr_dev, int dt, void* stream);
 int can_adam(float* p, float* m, float* v, const float* g, size_t n, float lr, double beta1, double beta2, float eps,
              float wd, int decoupled, float gscale, int step, int* t_dev, float* flags, const float* lr_dev,
-             void* stream);
+             void* stream, const float* gmul);
 int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
                  long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
-                 int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt, void* stream);
+                 int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt, void* stream,
+                 const float* gmul);
+// gradient-norm pass over the fp32 arena (two launches, fixed order) and the accumulation window's loss tick
+int can_grad_norm_chunk();
+int can_grad_norm(const float* g, const long long* tab, int np, long long max_count, double* part, float* gn,
+                  float gscale, float max_norm, float* flag, void* stream);
+int can_accum_tick(float* flags, float* acc, int fold, int close, void* stream);
 int can_img_to_nhwc4(const float* img, void* out, int N, int H, int W, int dt, void* stream);
 
 // context.hip

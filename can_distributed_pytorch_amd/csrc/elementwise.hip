@@ -251,13 +251,17 @@ __global__ void __launch_bounds__(1024) head_reduce_kernel(const float* __restri
 __global__ void __launch_bounds__(256) sgd_momentum_kernel(float4* __restrict__ p, float4* __restrict__ buf,
                                                            const float4* __restrict__ g, size_t n4, float lr,
                                                            float momentum, float gscale, int first,
-                                                           float* __restrict__ flags, const float* __restrict__ lr_dev) {
+                                                           float* __restrict__ flags, const float* __restrict__ lr_dev,
+                                                           const float* __restrict__ gmul) {
   if (flags != nullptr) {
     const bool bad_loss = flags[0] != 0.f;
     if (bad_loss && blockIdx.x == 0 && threadIdx.x == 0) flags[3] = 1.f;
     if (bad_loss || flags[2] != 0.f) return;
   }
   if (lr_dev != nullptr) lr = lr_dev[0];
+  // gmul (optional): a device-side gradient multiplier (the clip coefficient of grad_norm_final_kernel), folded into
+  // gscale by ONE fp32 product per thread, so the step equals passing float(gscale) * float(gmul[0]) from the host
+  if (gmul != nullptr) gscale = __fmul_rn(gscale, gmul[0]);
   for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     float4 gv = g[i];
     gv.x = __fmul_rn(gv.x, gscale); gv.y = __fmul_rn(gv.y, gscale);
@@ -423,6 +427,7 @@ struct OptArgs {
   const float* lr_dev;
   const int* t;                // Adam: applied steps so far, on the device (advanced by opt_tick_kernel); null:
   int step;                    //   this call's 1-based step from the host instead
+  const float* gmul;           // device gradient multiplier (clip coefficient): gscale *= gmul[0], once per thread; null: none
 };
 
 // ---- Adam (torch.optim.Adam / AdamW, no amsgrad, no maximize), fp32 per element:
@@ -442,7 +447,7 @@ __device__ __forceinline__ AdamCoef adam_coef(const OptArgs& a, float lr) {
   const int t = (a.t != nullptr) ? a.t[0] + 1 : a.step;
   const double bc1 = 1.0 - powi(a.beta1, (unsigned)t), bc2 = 1.0 - powi(a.beta2, (unsigned)t);
   AdamCoef c;
-  c.gscale = a.gscale;
+  c.gscale = (a.gmul != nullptr) ? __fmul_rn(a.gscale, a.gmul[0]) : a.gscale;
   c.cwd = a.decoupled ? 0.f : a.wd;
   c.decay = a.decoupled ? (float)(1.0 - (double)lr * (double)a.wd) : 1.f;
   c.w1 = (float)(1.0 - a.beta1);
@@ -492,6 +497,9 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
       if (bad_loss || sa.flags[2] != 0.f) return;
     }
     if (sa.lr_dev != nullptr) lr = sa.lr_dev[0];
+    if constexpr (OPT != OPT_ADAM) {              // (Adam: adam_coef folds gmul in)
+      if (sa.gmul != nullptr) sa.gscale = __fmul_rn(sa.gscale, sa.gmul[0]);
+    }
   }
   AdamCoef ac{};                // Adam: filled in below, past the exits of the blocks that have no work
   // one element of the SGD step (sgd_momentum_kernel's order of operations)
@@ -728,6 +736,92 @@ __global__ void opt_tick_kernel(const float* __restrict__ flags, int* __restrict
   t[0] += 1;
 }
 
+// ---------------------------------------------------------------- gradient norm (global-norm clipping)
+// Segmented sum of squares over the fp32 gradient arena in two launches, no atomics, fixed order (bitwise repeatable).
+// tab: {arena offset, element count} per parameter, in arena order (int64 pairs).
+// Stage 1, grid (chunk, parameter): block (c, p) sums the squares of elements [c*kNormChunk, (c+1)*kNormChunk) of
+// parameter p in double from the first add (the kernel reads the arena once and is bandwidth-bound) -- 16-byte loads
+// where the parameter starts 16-byte aligned (chunks keep the alignment), element-wise otherwise -- then reduces over
+// the wave by shuffles and over the four waves through LDS in wave order, and writes part[p * max_chunks + c].
+constexpr int kNormChunk = 4096;
+__global__ void __launch_bounds__(256) grad_norm_partial_kernel(const float* __restrict__ g,
+                                                                const long long* __restrict__ tab,
+                                                                double* __restrict__ part, int max_chunks) {
+  __shared__ double red[4];
+  const int p = blockIdx.y;
+  const long long off = tab[2 * p], n = tab[2 * p + 1];
+  const long long s0 = (long long)blockIdx.x * kNormChunk;
+  if (s0 >= n) return;
+  const int cnt = (int)min((long long)kNormChunk, n - s0);
+  const float* x = g + off + s0;
+  double s = 0.0;
+  if ((reinterpret_cast<uintptr_t>(g + off) & 15) == 0) {
+    const int n4 = cnt >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      const float4 v = reinterpret_cast<const float4*>(x)[i];
+      s = fma((double)v.x, (double)v.x, s); s = fma((double)v.y, (double)v.y, s);
+      s = fma((double)v.z, (double)v.z, s); s = fma((double)v.w, (double)v.w, s);
+    }
+    for (int i = 4 * n4 + threadIdx.x; i < cnt; i += 256) s = fma((double)x[i], (double)x[i], s);
+  } else {
+    for (int i = threadIdx.x; i < cnt; i += 256) s = fma((double)x[i], (double)x[i], s);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[(size_t)p * max_chunks + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Stage 2, one block: thread p sums parameter p's partials in index order (its sum replaces the row's first partial),
+// then thread 0 sums the parameters in arena order and writes the fp32 vector gn:
+//   gn[0] = gscale * sqrt(total), the norm of the gradient the optimizer sees (gscale = 1 / world);
+//   gn[1] = the clip coefficient min(1, max_norm / (gn[0] + 1e-6)) (torch.nn.utils.clip_grad_norm_'s rule, in fp32;
+//           max_norm = inf: exactly 1);  gn[2 + p] = gscale * sqrt(parameter p's sum).
+// A double sum of squares of finite fp32 values cannot overflow, so a non-finite total means a non-finite element:
+// then gn[1] = 0 and flag[0] (the step's flags[2], which the optimizer kernels skip on) is set.
+__global__ void __launch_bounds__(256) grad_norm_final_kernel(const long long* __restrict__ tab, int np,
+                                                              double* __restrict__ part, int max_chunks,
+                                                              float* __restrict__ gn, float gscale, float max_norm,
+                                                              float* __restrict__ flag) {
+  for (int p = threadIdx.x; p < np; p += 256) {
+    const long long n = tab[2 * p + 1];
+    const int nc = (int)min((long long)max_chunks, (n + kNormChunk - 1) / kNormChunk);
+    double* row = part + (size_t)p * max_chunks;
+    double s = 0.0;
+    for (int c = 0; c < nc; ++c) s += row[c];
+    row[0] = s;
+    gn[2 + p] = (float)((double)gscale * sqrt(s));
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double total = 0.0;
+  for (int p = 0; p < np; ++p) total += part[(size_t)p * max_chunks];
+  if (!isfinite(total)) {
+    gn[0] = (float)total;
+    gn[1] = 0.f;
+    if (flag != nullptr) flag[0] = 1.f;
+    return;
+  }
+  const float norm = (float)((double)gscale * sqrt(total));
+  gn[0] = norm;
+  gn[1] = fminf(1.f, max_norm / (norm + 1e-6f));
+}
+
+// Gradient accumulation: folds the micro-batch loss the fused head just wrote to flags[1] into a device accumulator
+// (one thread, like opt_tick_kernel).  fold: 1 = the window's first micro-step (set), 2 = a later one (add), 0 = none
+// (a window closed by flush(), whose micro-steps are all folded already); close: the window's total goes back to
+// flags[1] and its non-finite flag to flags[0], ahead of the loss all-reduce.
+__global__ void accum_tick_kernel(float* __restrict__ flags, float* __restrict__ acc, int fold, int close) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float a = (fold == 1) ? flags[1] : (fold == 2) ? acc[0] + flags[1] : acc[0];
+  acc[0] = a;
+  if (close) {
+    flags[1] = a;
+    flags[0] = isfinite(a) ? 0.f : 1.f;
+  }
+}
+
 static inline int grid_for(size_t n, int per = 256, int cap = 4096) {
   size_t g = (n + per - 1) / per;
   if (g > (size_t)cap) g = cap;
@@ -793,10 +887,12 @@ extern "C" int can_head_train(const void* y, const float* w, const float* b, con
 }
 
 extern "C" int can_sgd_momentum(float* p, float* buf, const float* g, size_t n, float lr, float momentum,
-                                float gscale, int first, float* flags, const float* lr_dev, void* stream) {
+                                float gscale, int first, float* flags, const float* lr_dev, void* stream,
+                                const float* gmul) {
   if (n & 3) return -2;
   hipLaunchKernelGGL(sgd_momentum_kernel, dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
-                     (float4*)p, (float4*)buf, (const float4*)g, n / 4, lr, momentum, gscale, first, flags, lr_dev);
+                     (float4*)p, (float4*)buf, (const float4*)g, n / 4, lr, momentum, gscale, first, flags, lr_dev,
+                     gmul);
   return (int)hipGetLastError();
 }
 
@@ -891,12 +987,12 @@ extern "C" int can_sgd_pack(const long long* desc, int rows, int max_tiles, long
 // so far; advanced by one here unless the step is skipped through flags); null: `step` is this call's 1-based step.
 extern "C" int can_adam(float* p, float* m, float* v, const float* g, size_t n, float lr, double beta1, double beta2,
                         float eps, float wd, int decoupled, float gscale, int step, int* t_dev, float* flags,
-                        const float* lr_dev, void* stream) {
+                        const float* lr_dev, void* stream, const float* gmul) {
   if (n == 0) return 0;
   if (t_dev == nullptr && step < 1) return -2;
   OptArgs a{};
   a.lr = lr; a.gscale = gscale; a.wd = wd; a.eps = eps; a.decoupled = decoupled; a.beta1 = beta1; a.beta2 = beta2;
-  a.flags = flags; a.lr_dev = lr_dev; a.t = t_dev; a.step = step;
+  a.flags = flags; a.lr_dev = lr_dev; a.t = t_dev; a.step = step; a.gmul = gmul;
   const int vec = (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(vec ? (n + 3) / 4 : n, 256, 4096)), dim3(256), 0, s, p, m, v, g, n, vec,
@@ -910,14 +1006,14 @@ extern "C" int can_adam(float* p, float* m, float* v, const float* g, size_t n, 
 extern "C" int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
                             long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
                             int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt,
-                            void* stream) {
+                            void* stream, const float* gmul) {
   if (rows <= 0) return 0;
   if (opt < OPT_SGD || opt > OPT_ADAM || (opt == OPT_ADAM && t_dev == nullptr)) return -2;
   if (dt != DT_F16 && dt != DT_BF16) return -20;
   OptArgs sa{};
   sa.goff = goff; sa.boff = boff; sa.voff = (opt == OPT_ADAM) ? voff : 0;
   sa.lr = lr; sa.momentum = momentum; sa.gscale = gscale; sa.wd = wd; sa.eps = eps; sa.decoupled = decoupled;
-  sa.beta1 = beta1; sa.beta2 = beta2; sa.flags = flags; sa.lr_dev = lr_dev; sa.t = t_dev;
+  sa.beta1 = beta1; sa.beta2 = beta2; sa.flags = flags; sa.lr_dev = lr_dev; sa.t = t_dev; sa.gmul = gmul;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(max_tiles, rows), blk(256);
 #define CAN_OPT_LAUNCH(O)                                                                                       \
@@ -932,5 +1028,28 @@ extern "C" int can_opt_pack(const long long* desc, int rows, int max_tiles, int 
     hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t_dev);
   }
 #undef CAN_OPT_LAUNCH
+  return (int)hipGetLastError();
+}
+
+// The gradient-norm pass (grad_norm_partial_kernel + grad_norm_final_kernel).  tab: np {offset, count} int64 pairs on
+// the device; max_count: the largest count (host copy); part: np * ceil(max_count / 4096) doubles of scratch;
+// gn: 2 + np floats; flag: the step's flags + 2 (optional).
+extern "C" int can_grad_norm_chunk() { return kNormChunk; }
+extern "C" int can_grad_norm(const float* g, const long long* tab, int np, long long max_count, double* part, float* gn,
+                             float gscale, float max_norm, float* flag, void* stream) {
+  if (np <= 0 || max_count < 0 || !(max_norm >= 0.f)) return -2;
+  const long long mc = (max_count + kNormChunk - 1) / kNormChunk;
+  if (mc > 0x7fffffffll || np > 65535) return -3;
+  const int max_chunks = mc < 1 ? 1 : (int)mc;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(max_chunks, np), dim3(256), 0, s, g, tab, part, max_chunks);
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, s, tab, np, part, max_chunks, gn, gscale, max_norm,
+                     flag);
+  return (int)hipGetLastError();
+}
+
+extern "C" int can_accum_tick(float* flags, float* acc, int fold, int close, void* stream) {
+  if (fold < 0 || fold > 2) return -2;
+  hipLaunchKernelGGL(accum_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, flags, acc, fold, close);
   return (int)hipGetLastError();
 }

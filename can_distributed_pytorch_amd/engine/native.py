@@ -43,6 +43,12 @@ re-designed for MI355X:
   after the all-reduce makes the fused SGD skip the step, and a one-thread
   kernel backs the scale off / grows it (GradScaler semantics: x0.5 on
   overflow, x2 after ``scale_interval`` clean steps).
+* ``accum_steps=k`` makes k micro-steps one optimizer step on the SUM of their gradients (the sum-reduced loss needs
+  no 1/k; lr is NOT rescaled by k): the opening micro-step overwrites the gradient arena (beta 0), later ones add to
+  it (beta 1), and only the closing one runs the reducer, the loss all-reduce, the optimizer and the loss-scale
+  update; ``clip_grad_norm=m`` adds a two-launch fixed-order norm pass over the accumulated, all-reduced arena whose
+  clip coefficient the optimizer kernel reads from the device (``_step_tail``, README "Gradient accumulation and
+  clipping").  With the defaults the step issues exactly the launches it issued before.
 
 CU budget of the gradient all-reduce (``comm_ctas``, default 8 = parallel.reducer.DEFAULT_COMM_CTAS): the owned RCCL
 communicator is created with ncclConfig_t.minCTAs = maxCTAs = comm_ctas, so its kernels occupy exactly that many of
@@ -157,9 +163,14 @@ class NativeStepper:
                  graph=True, model: Optional[CANNet] = None, reducer=None, bucket_mb: float = 25.0,
                  reducer_transport: Optional[str] = None, init_scale="auto", scale_interval: int = 2000,
                  graph_max_shapes: int = 8, comm_ctas: Optional[int] = None, graph_bind_inputs: bool = False,
-                 optimizer: str = "sgd", weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
+                 optimizer: str = "sgd", weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
+                 accum_steps: int = 1, clip_grad_norm: float = 0.0):
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+        if int(accum_steps) != accum_steps or accum_steps < 1:
+            raise ValueError(f"accum_steps must be an integer >= 1, got {accum_steps!r}")
+        if not clip_grad_norm >= 0:
+            raise ValueError(f"clip_grad_norm must be >= 0 (0 = off, inf = measure only), got {clip_grad_norm!r}")
         if dtype not in ACT_DTYPES:
             raise ValueError(f"the native step computes in bf16 or fp16 (fp32 master weights), got {dtype!r}; "
                              "use --impl torch for fp32")
@@ -190,6 +201,19 @@ class NativeStepper:
         self.ex.opt_prepare(self.arena.data, self.arena.grad, self.mom, self.mom2)   # (device descriptor: before any capture)
         # [non-finite loss (any rank after the all-reduce), loss, non-finite gradient (fp16), sticky non-finite]
         self.flags = torch.zeros(4, dtype=torch.float32, device=self.device)
+        # gradient accumulation: a window of accum_steps micro-steps is ONE optimizer step on the sum of their
+        # gradients (the loss is a sum-reduced MSE, so that is the batch's gradient: no 1/k, and lr is NOT rescaled
+        # by accum_steps).  _micro = micro-steps run in the open window; _acc = the window's loss so far (device)
+        self.accum_steps = int(accum_steps)
+        self._micro = 0
+        self._acc = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._warm = set()                           # input shapes an eager step or a capture warm-up has run
+        # global-norm clipping (0 = off): the norm pass over the accumulated, all-reduced gradient right before the
+        # optimizer, which reads the clip coefficient from the device (gn[1])
+        self.clip_grad_norm = float(clip_grad_norm)
+        self.gn = None
+        if self.clip_grad_norm > 0:
+            self.gn = self.ex.norm_prepare(self.arena.grad, [self.arena.offsets[i] for i in self.arena.order])
         self._lr_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.lr = lr * world                       # train.py:25 linear scaling
         # fp16: device-side dynamic loss scale {S, 1/S, clean steps, 0}
@@ -260,21 +284,32 @@ class NativeStepper:
         self._lr = float(v)
         self._lr_dev.fill_(self._lr)
 
-    def _step_body(self, img, gt, update: bool = True):
-        self._step_fwd_bwd(img, gt)
-        return self._step_tail(update)
+    # A micro-step's phase within its accumulation window is (opening, closing); accum_steps = 1: always WHOLE.
+    #   opening: head and backward overwrite the gradient arena (beta 0), later micro-steps add to it (beta 1);
+    #   closing: the reducer runs and the full tail follows (loss tick, loss / flag all-reduce, norm pass or overflow
+    #   check, optimizer, loss-scale update); a non-closing micro-step leaves the reducer idle and its tail is the
+    #   loss tick alone (the side stream is still joined before the next forward).
+    WHOLE = (True, True)
 
-    def _step_fwd_bwd(self, img, gt):
+    def _phase(self):
+        return (self._micro == 0, self._micro + 1 >= self.accum_steps)
+
+    def _step_body(self, img, gt, update: bool = True, phase=WHOLE):
+        self._step_fwd_bwd(img, gt, phase)
+        return self._step_tail(update, phase)
+
+    def _step_fwd_bwd(self, img, gt, phase=WHOLE):
         """Forward, fused head + loss, backward (gradients into the arena, buckets handed to the reducer)."""
         ex = self.ex
+        beta = 0.0 if phase[0] else 1.0
         with trace_range("cannet/forward"):
             b6, sv = ex.forward_features(img, save=True)
             ex.workspace(*ex.input_hw(img))
             sc = self.scaler
             # fused head: loss -> flags[1], its non-finite flag -> flags[0] (same kernel, no extra launch)
             loss, et, d_b6 = ex.head_train(b6, gt, self.grads, lscale=sc[0:1] if sc is not None else None,
-                                           flags=self.flags)
-        red = self.reducer
+                                           flags=self.flags, beta=beta)
+        red = self.reducer if phase[1] else None
         timing = self.comm_timing and self.device.type == "cuda"
         if red is not None:
             red.set_timing(timing)
@@ -282,15 +317,21 @@ class NativeStepper:
             red.mark_ready([ex.head_w_index, ex.head_b_index])
         with trace_range("cannet/backward"):
             ex.backward_features(sv, d_b6, self.grads, on_grad_ready=(red.mark_ready if red is not None else None),
-                                 dscale=sc[1:2] if sc is not None else None)
+                                 dscale=sc[1:2] if sc is not None else None, beta=beta)
         del sv
 
-    def _step_tail(self, update: bool = True):
-        """All-reduce join, fp16 overflow check, fused SGD + weight packs, loss-scale update."""
+    def _step_tail(self, update: bool = True, phase=WHOLE, fold: bool = True):
+        """All-reduce join, fp16 overflow check, fused SGD + weight packs, loss-scale update.  Accumulation: the loss
+        tick first; a non-closing micro-step ends there (returns None)."""
         ex = self.ex
         st = _ext.stream_ptr(self.device)
         sc = self.scaler
         red = self.reducer
+        if self.accum_steps > 1 and update:
+            self.C.accum_tick(self.flags.data_ptr(), self._acc.data_ptr(), (1 if phase[0] else 2) if fold else 0,
+                              int(phase[1]), st)
+        if not phase[1]:
+            return None
         timing = self.comm_timing and self.device.type == "cuda"
         if timing:
             e0 = torch.cuda.Event(enable_timing=True)
@@ -305,7 +346,13 @@ class NativeStepper:
             self._comm_events.append((e0, e1))
             if red is not None:
                 self._bucket_reports.append(red.timings())
-        if sc is not None:
+        clip = self.gn is not None
+        if clip:
+            # the norm of the accumulated, all-reduced gradient (every rank: the same value); a non-finite element
+            # sets flags[2], so in fp16 this one read of the arena is also the overflow check
+            self.flags[2:3].zero_()
+            ex.grad_norm(1.0 / self.world, self.clip_grad_norm, self.flags)
+        elif sc is not None:
             # after the all-reduce every rank holds the same gradients -> the same verdict
             self.flags[2:3].zero_()
             self.C.grad_nonfinite(self.arena.grad.data_ptr(), self.arena.numel, self.flags.data_ptr() + 8, st)
@@ -313,14 +360,14 @@ class NativeStepper:
             return self.flags[1:2]
         with trace_range("cannet/sgd"):
             # the optimizer over the arena and the 16-bit weight packs in ONE launch (executor.sgd_step / opt_step)
-            if self.optimizer == "sgd" and self.weight_decay == 0:
+            if self.optimizer == "sgd" and self.weight_decay == 0 and not clip:
                 ex.sgd_step(self.arena.data, self.arena.grad, self.mom, self._lr, self.momentum, 1.0 / self.world,
                             flags=self.flags, lr_dev=self._lr_dev)
             else:
                 ex.opt_step(self.arena.data, self.arena.grad, self.mom, self._lr, 1.0 / self.world,
                             optimizer=self.optimizer, momentum=self.momentum, weight_decay=self.weight_decay,
                             betas=self.betas, eps=self.eps, mom2=self.mom2, step=self.opt_t, flags=self.flags,
-                            lr_dev=self._lr_dev)
+                            lr_dev=self._lr_dev, gmul=self.gn[1:2] if clip else None)
             if sc is not None:
                 self.C.scale_update(self.flags.data_ptr() + 8, sc.data_ptr(), int(self.scale_interval), 2.0, 0.5,
                                     float(2 ** 24), st)
@@ -377,6 +424,9 @@ class NativeStepper:
         return n * h * w <= self.AUTO_GRAPH_PIXELS
 
     def step(self, img, gt):
+        """One micro-step.  Returns the loss (summed over ranks; with accum_steps > 1: over the window's micro-batches
+        too) as a device scalar on the call that closes a window, None on the others.  ``skipped_last()``, the sticky
+        non-finite flag, Adam's step count and the fp16 loss scale all advance per window."""
         if img.device != self.device:
             img = img.to(self.device, non_blocking=True)
         if gt.device != self.device:
@@ -384,22 +434,30 @@ class NativeStepper:
         if self._auto_scale:
             self._auto_scale = False
             self.calibrate_loss_scale(img, gt)
-        key = (tuple(img.shape), img.dtype, tuple(gt.shape))
+        shape_key = key = (tuple(img.shape), img.dtype, tuple(gt.shape))
         if self.graph_bind_inputs:
             key += (img.data_ptr(), gt.data_ptr())
+        phase = self._phase()
+        if self.accum_steps > 1:
+            key += (phase,)                  # a window's phases differ in beta and in the tail: one graph each
         use = self._wants_graph(img)
         if use and self.use_graph == "auto" and key not in self._graphs:
             # auto: capture a shape on its SECOND occurrence (a one-off size of a mixed-size set runs eager)
             self._seen[key] += 1
             use = self._seen[key] >= 2
+        ent = self._graphs.get(key) if use else None
+        if use and ent is None and not phase[0] and shape_key not in self._warm:
+            # a shape first met inside an open window: _capture's warm-up (a real forward / backward into the
+            # gradient arena) would clobber the window, so this occurrence runs eagerly as the real micro-step --
+            # the same kernels on the same shapes, which is all the warm-up is for -- and the next one captures
+            use = False
         if not use:
-            out = self._eager_body(img, gt)
-            self._loss = out
-            self.steps += 1
-            return out
-        ent = self._graphs.get(key)
+            out = self._eager_body(img, gt, phase=phase)
+            self._warm.add(shape_key)
+            return self._advance(out, phase)
         if ent is None:
-            ent = self._capture(img, gt, key)
+            ent = self._capture(img, gt, key, phase=phase, warm=shape_key not in self._warm or phase[0])
+            self._warm.add(shape_key)
         else:
             self._graphs.move_to_end(key)
         self.graph, self.static_img, self.static_gt, self._static_loss = ent
@@ -408,25 +466,65 @@ class NativeStepper:
         if self.static_gt.data_ptr() != gt.data_ptr():
             self.static_gt.copy_(gt, non_blocking=True)
         self.graph.replay()
-        self._loss = self._static_loss
+        return self._advance(self._static_loss, phase)
+
+    def _advance(self, out, phase):
         self.steps += 1
-        return self._static_loss
+        self._micro = 0 if phase[1] else self._micro + 1
+        if phase[1]:
+            self._loss = out
+        return out
+
+    def flush(self):
+        """Close an open accumulation window now (the end of an epoch: no sample is dropped, nothing leaks into the
+        next epoch, a checkpoint never sees an open window): the reducer over the accumulated arena, then the full
+        tail, eagerly.  Returns the window's loss, or None when no window is open."""
+        if self._micro == 0:
+            return None
+        red = self.reducer
+        if red is not None:
+            red.set_timing(False)
+            red.begin()
+            red.mark_ready(list(self.arena.order))
+        out = self._step_tail(True, phase=(False, True), fold=False)
+        self._micro = 0
+        self._loss = out
+        return out
+
+    def grad_norm(self) -> Optional[float]:
+        """Global 2-norm of the last window's accumulated, averaged gradient, before clipping (None: clipping off).
+        Synchronises the host, as ``grad_norms`` and ``clip_coef``: meant for the logging cadence."""
+        return None if self.gn is None else float(self.gn[0].item())
+
+    def clip_coef(self) -> Optional[float]:
+        """The coefficient the last window's gradient was multiplied by (0: skipped on a non-finite gradient)."""
+        return None if self.gn is None else float(self.gn[1].item())
+
+    def grad_norms(self) -> Optional[dict]:
+        """Parameter name -> 2-norm of its gradient in the last window."""
+        if self.gn is None:
+            return None
+        names = [n for n, _ in self.model.named_parameters()]
+        v = self.gn[2:].tolist()
+        return {names[i]: v[j] for j, i in enumerate(self.arena.order)}
 
     def _ws_ptr(self):
         ws = self.ex.ws
         return None if ws is None else ws.buf.data_ptr()
 
-    def _eager_body(self, img, gt, update: bool = True):
+    def _eager_body(self, img, gt, update: bool = True, phase=WHOLE):
         """An eager step; if it grew the shared weight-gradient workspace (a larger shape), every captured graph
         points at the released buffer and is dropped."""
         before = self._ws_ptr()
         # (the step on a high-priority stream measured -1 % at batch 1, profiles/r5/ab_hp_step.jsonl: removed)
-        out = self._step_body(img, gt, update=update)
+        out = self._step_body(img, gt, update=update, phase=phase)
         if self._graphs and self._ws_ptr() != before:
             self._graphs.clear()
         return out
 
-    def _capture(self, img, gt, key=None):
+    def _capture(self, img, gt, key=None, phase=WHOLE, warm: bool = True):
+        """warm = False: the shape has run before (its opening phase's warm-up or an eager micro-step), and this
+        phase's capture must not run a real backward into the open window's gradient arena."""
         key = key if key is not None else (tuple(img.shape), img.dtype, tuple(gt.shape))
         while len(self._graphs) >= max(1, self.graph_max_shapes):
             self._graphs.popitem(last=False)             # LRU: its graph and private memory pool are released
@@ -434,21 +532,23 @@ class NativeStepper:
         static_gt = gt if self.graph_bind_inputs else gt.clone()
         # warm up on a side stream (allocations, workspace sizing, kernel attrs); a grown workspace drops the
         # graphs captured before (_eager_body)
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            self._eager_body(static_img, static_gt, update=False)
-        torch.cuda.current_stream(self.device).wait_stream(s)
+        if warm:
+            s = torch.cuda.Stream(self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(s):
+                self._eager_body(static_img, static_gt, update=False)
+            torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
         side = self.ex._side_stream()
         nat = getattr(self.reducer, "_native", None) if self.reducer is not None else None
         if side is not None and (self.reducer is None or nat is not None):
-            g, loss = self._capture_split(static_img, static_gt, side.cuda_stream, nat)
+            # (a non-closing micro-step leaves the reducer idle: no comm graph)
+            g, loss = self._capture_split(static_img, static_gt, side.cuda_stream, nat if phase[1] else None, phase)
         else:
             # torch-transport reducer (its collectives are torch.distributed works) or no side stream: one graph
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self._shared_pool()):
-                loss = self._step_body(static_img, static_gt)
+                loss = self._step_body(static_img, static_gt, phase=phase)
         torch.cuda.synchronize(self.device)
         ent = (g, static_img, static_gt, loss)
         self._graphs[key] = ent
@@ -465,7 +565,7 @@ class NativeStepper:
             self._graph_pool = torch.cuda.graph_pool_handle()
         return self._graph_pool
 
-    def _capture_split(self, static_img, static_gt, side: int, nat=None):
+    def _capture_split(self, static_img, static_gt, side: int, nat=None, phase=WHOLE):
         """Capture the step as compute graph A + side graph (+ comm graph) + compute graph B (SplitCapture).
         nat: the native RCCL BucketReducer, whose comm stream is captured as its own graph spanning A and B (its
         bucket all-reduces are issued during A, its end is recorded by finish() during B)."""
@@ -484,7 +584,7 @@ class NativeStepper:
                     C.capture_begin(comm)
                     comm_open = True
                 try:
-                    self._step_fwd_bwd(static_img, static_gt)
+                    self._step_fwd_bwd(static_img, static_gt, phase)
                 finally:
                     sc.side_graph = C.capture_end(side)
             # (not torch.cuda.graph: its __enter__ synchronises the device, which a stream still capturing -- the
@@ -495,7 +595,7 @@ class NativeStepper:
                 b.capture_begin(pool=self._shared_pool(), capture_error_mode="relaxed")
                 try:
                     C.wait_external(_ext.stream_ptr(self.device), sc.end_event)
-                    loss = self._step_tail(True)
+                    loss = self._step_tail(True, phase)
                 finally:
                     b.capture_end()
         finally:

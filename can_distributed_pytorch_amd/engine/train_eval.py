@@ -17,6 +17,7 @@ the same cadence and at the end of the epoch.
 """
 from __future__ import annotations
 
+import contextlib
 import itertools
 import random
 import sys
@@ -38,18 +39,41 @@ def _progress(it, enabled):
         return it
 
 
-def train_one_epoch(model, optimizer, train_loader, device, epoch, log=None):
-    """Generic autograd path (any model/optimizer, DDP or our hook reducer)."""
+def train_one_epoch(model, optimizer, train_loader, device, epoch, log=None, accum_steps: int = 1,
+                    clip_grad_norm: float = 0.0):
+    """Generic autograd path (any model/optimizer, DDP or our hook reducer).
+
+    accum_steps > 1: one optimizer step per window of accum_steps batches on the sum of their gradients (the loss is
+    sum-reduced: no 1/k, lr not rescaled) -- zero_grad at a window's start, DDP ``no_sync()`` on its non-closing
+    batches, and a window still open at the end of the epoch is closed there (for DDP the loader's last batch always
+    runs synchronised, so that flush has the all-reduced gradient).  clip_grad_norm > 0:
+    torch.nn.utils.clip_grad_norm_ ahead of every optimizer step."""
     model.train()
     criterion = torch.nn.MSELoss(reduction="sum")
     mean_loss = torch.zeros(1, device=device)
     loader = _progress(train_loader, is_main_process())
+    params = [p for p in model.parameters() if p.requires_grad]
+    try:
+        last = len(train_loader) - 1
+    except TypeError:
+        last = -1
+    micro = 0
+
+    def apply():
+        if clip_grad_norm > 0:
+            torch.nn.utils.clip_grad_norm_([p for p in params if p.grad is not None], clip_grad_norm)
+        optimizer.step()
+
     for step, (img, gt) in enumerate(loader):
-        optimizer.zero_grad()
+        if micro == 0:
+            optimizer.zero_grad()
+        closing = micro + 1 >= accum_steps or step == last
         img, gt = img.to(device, non_blocking=True), gt.to(device, non_blocking=True)
-        et = model(img)
-        loss = criterion(et, gt)
-        loss.backward()
+        with (model.no_sync() if not closing and hasattr(model, "no_sync") else contextlib.nullcontext()):
+            et = model(img)
+            loss = criterion(et, gt)
+            loss.backward()
+        micro = 0 if closing else micro + 1
         loss = reduce_value(loss.detach(), average=True)
         mean_loss = (mean_loss * step + loss) / (step + 1)
         if is_main_process() and hasattr(loader, "desc"):
@@ -57,7 +81,10 @@ def train_one_epoch(model, optimizer, train_loader, device, epoch, log=None):
         if not torch.isfinite(loss):
             print("WARNING: non-finite loss, ending training ", loss)
             sys.exit(1)
-        optimizer.step()
+        if closing:
+            apply()
+    if micro:
+        apply()                                   # (a loader without a length: the open window's flush)
     if torch.device(device).type == "cuda":
         torch.cuda.synchronize(device)
     return mean_loss.item()
@@ -76,7 +103,15 @@ def train_one_epoch_native(stepper, train_loader, device, epoch, log=None, log_e
     pix = 0
     ahead = prep is not None and hasattr(prep, "issue")      # ops/preprocess.py AheadPrep: one batch ahead
     it = iter(loader)
-    pending = prep.issue(next(it)) if ahead else None
+    first = next(it, None) if ahead else None                # (an empty loader: nothing to issue)
+    pending = prep.issue(first) if first is not None else None
+    clip = getattr(stepper, "clip_grad_norm", 0.0) > 0
+
+    def add(loss):
+        # a window's loss arrives on the call that closes it (None on the others); the running mean stays "sum of
+        # losses / number of micro-batches", the reference's meaning at accum_steps = 1
+        if loss is not None:
+            total.add_(loss.reshape(1) / max(1, get_world_size()))
     for step in itertools.count():
         if ahead:
             if pending is None:
@@ -91,7 +126,7 @@ def train_one_epoch_native(stepper, train_loader, device, epoch, log=None, log_e
                 break
             img, gt = prep(batch) if prep is not None else batch
             loss = stepper.step(img, gt)      # SUM of the per-rank losses (averaged below)
-        total += loss.reshape(1) / max(1, get_world_size())
+        add(loss)
         n += 1
         imgs += img.shape[0] * get_world_size()
         # NHWC4 (GPU-preprocessed) or NCHW input: per-pixel throughput for variable-size images
@@ -107,7 +142,12 @@ def train_one_epoch_native(stepper, train_loader, device, epoch, log=None, log_e
                     loader.desc = f"[epoch {epoch}] mean loss {round(ml, 3)}"
                 if log is not None:
                     dt = time.perf_counter() - t0
-                    log.log(kind="train", epoch=epoch, step=step + 1, mean_loss=ml, imgs_per_s=imgs / max(dt, 1e-9))
+                    rec = dict(kind="train", epoch=epoch, step=step + 1, mean_loss=ml, imgs_per_s=imgs / max(dt, 1e-9))
+                    if clip:
+                        rec.update(grad_norm=stepper.grad_norm(), clip_coef=stepper.clip_coef())
+                    log.log(**rec)
+    if hasattr(stepper, "flush"):
+        add(stepper.flush())                      # an open accumulation window ends with the epoch
     if torch.device(device).type == "cuda":
         torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0

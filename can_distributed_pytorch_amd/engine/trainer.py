@@ -15,6 +15,7 @@ step (utils/train_eval_utils.py:28-52):
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import torch
@@ -24,6 +25,13 @@ from ..models.cannet import CANNet
 
 
 OPTIMIZERS = ("sgd", "adam", "adamw")
+
+
+def _check_window(accum_steps, clip_grad_norm):
+    if int(accum_steps) != accum_steps or accum_steps < 1:
+        raise ValueError(f"accum_steps must be an integer >= 1, got {accum_steps!r}")
+    if not clip_grad_norm >= 0:
+        raise ValueError(f"clip_grad_norm must be >= 0 (0 = off, inf = measure only), got {clip_grad_norm!r}")
 
 
 def make_torch_optimizer(params, optimizer="sgd", lr=1e-7, momentum=0.95, weight_decay=0.0, betas=(0.9, 0.999),
@@ -42,7 +50,17 @@ class TorchStepper:
     exec_backend = "torch"
 
     def __init__(self, device, dtype="fp32", world=1, lr=1e-7, momentum=0.95, channels_last=None, model=None,
-                 bucket_mb: float = 25.0, optimizer="sgd", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
+                 bucket_mb: float = 25.0, optimizer="sgd", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8,
+                 accum_steps: int = 1, clip_grad_norm: float = 0.0):
+        _check_window(accum_steps, clip_grad_norm)
+        # gradient accumulation / global-norm clipping, the stock way: zero_grad at a window's start, DDP no_sync()
+        # on its non-closing micro-steps, torch.nn.utils.clip_grad_norm_ ahead of the optimizer (engine/native.py has
+        # the semantics: the sum-reduced loss needs no 1/k, lr is not rescaled)
+        self.accum_steps = int(accum_steps)
+        self.clip_grad_norm = float(clip_grad_norm)
+        self._micro = 0
+        self._acc = None
+        self._grad_norm = None
         self.device = torch.device(device)
         self.model = (model or CANNet(backend=self.exec_backend)).to(self.device)
         self.model.exec_backend = self.exec_backend
@@ -65,25 +83,56 @@ class TorchStepper:
         self.scaler = torch.amp.GradScaler("cuda") if dtype == "fp16" else None
 
     def step(self, img, gt):
-        self.opt.zero_grad(set_to_none=True)
+        """One micro-step; returns the window's loss on the call that closes it (accum_steps = 1: every call), else
+        None."""
+        closing = self._micro + 1 >= self.accum_steps
+        if self._micro == 0:
+            self.opt.zero_grad(set_to_none=True)
         if self.channels_last:
             img = img.contiguous(memory_format=torch.channels_last)
-        if self.autocast is not None:
-            with torch.autocast(self.device.type, dtype=self.autocast):
+        sync = contextlib.nullcontext() if closing or self.net is self.model else self.net.no_sync()
+        with sync:
+            if self.autocast is not None:
+                with torch.autocast(self.device.type, dtype=self.autocast):
+                    et = self.net(img)
+                loss = self.crit(et.float(), gt)
+            else:
                 et = self.net(img)
-            loss = self.crit(et.float(), gt)
-        else:
-            et = self.net(img)
-            loss = self.crit(et, gt)
+                loss = self.crit(et, gt)
+            if self.scaler is not None:
+                self.scaler.scale(loss).backward()
+            else:
+                loss.backward()
+        self._acc = loss.detach() if self._micro == 0 else self._acc + loss.detach()
+        self._micro += 1
+        if not closing:
+            return None
+        return self._finish_window()
+
+    def _finish_window(self):
+        if self.clip_grad_norm > 0:
+            if self.scaler is not None:
+                self.scaler.unscale_(self.opt)
+            self._grad_norm = torch.nn.utils.clip_grad_norm_(
+                [p for p in self.model.parameters() if p.grad is not None], self.clip_grad_norm)
         if self.scaler is not None:
-            self.scaler.scale(loss).backward()
             self.scaler.step(self.opt)
             self.scaler.update()
         else:
-            loss.backward()
             self.opt.step()
-        self._loss = loss.detach()
+        self._micro = 0
+        self._loss = self._acc
         return self._loss
+
+    def flush(self):
+        """Close an open window now (end of an epoch); None when no window is open.  (World > 1: the window's earlier
+        micro-steps ran under no_sync(), so call it only where every rank's window closes through step().)"""
+        if self._micro == 0:
+            return None
+        return self._finish_window()
+
+    def grad_norm(self) -> Optional[float]:
+        return None if self._grad_norm is None else float(self._grad_norm)
 
     def last_loss(self) -> Optional[float]:
         return None if self._loss is None else float(self._loss)
@@ -114,8 +163,15 @@ class ArenaStepper:
     exec_backend = "torch"
 
     def __init__(self, device="cpu", world=1, lr=1e-7, momentum=0.95, model=None, bucket_mb: float = 25.0,
-                 optimizer="sgd", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
+                 optimizer="sgd", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, accum_steps: int = 1,
+                 clip_grad_norm: float = 0.0):
         from ..models.cannet import grad_ready_order
+        _check_window(accum_steps, clip_grad_norm)
+        self.accum_steps = int(accum_steps)
+        self.clip_grad_norm = float(clip_grad_norm)
+        self._micro = 0
+        self._acc = None
+        self._gn = None                                      # (global norm, clip coefficient) of the last window
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         self.optimizer = optimizer
@@ -147,41 +203,91 @@ class ArenaStepper:
             self.reducer.broadcast_arena(0)
 
     def step(self, img, gt):
+        """One micro-step (the native step's window: engine/native.py): the arena is zeroed at a window's start only,
+        the reducer is paused on non-closing micro-steps (their autograd hooks launch nothing), and the closing one
+        all-reduces the accumulated gradient once.  Returns the window's loss on the closing call, else None."""
         red = self.reducer
+        closing = self._micro + 1 >= self.accum_steps
         red.set_timing(self.comm_timing)
-        self.arena.grad.zero_()
+        if self._micro == 0:
+            self.arena.grad.zero_()
         self.arena.attach_grads()                  # autograd accumulates into the arena views in place
-        red.begin()
+        red.paused = not closing
+        if closing:
+            red.begin()
         et = self.model(img.to(self.device))
         loss = self.crit(et, gt.to(self.device))
         loss.backward()
+        self._acc = loss.detach() if self._micro == 0 else self._acc + loss.detach()
+        self._micro += 1
+        if not closing:
+            return None
+        return self._finish_window()
+
+    def _finish_window(self):
+        red = self.reducer
         red.finish()
         if self.comm_timing:
             self._timings.append(red.timings())
         with torch.no_grad():
-            self.flags[0] = 0.0 if bool(torch.isfinite(loss)) else 1.0
-            self.flags[1] = loss.detach()
+            self.flags[0] = 0.0 if bool(torch.isfinite(self._acc)) else 1.0
+            self.flags[1] = self._acc
             red.allreduce_scalars(self.flags)
             if self.flags[0] == 0:
                 self._update()
+        self._micro = 0
         self._loss = self.flags[1:2] / self.world
         return self._loss
+
+    def flush(self):
+        """Close an open window now (reducer begin / every parameter ready / finish, then the tail); None when no
+        window is open."""
+        if self._micro == 0:
+            return None
+        red = self.reducer
+        red.paused = False
+        red.begin()
+        red.mark_ready(list(self.arena.order))
+        return self._finish_window()
+
+    def _clip(self) -> float:
+        """1 / world times the native norm kernel's coefficient min(1, max_norm / (||g / W|| + 1e-6)) in torch ops;
+        a non-finite norm skips the update (returns None), as the kernel's flags[2]."""
+        gs = 1.0 / self.world
+        if self.clip_grad_norm <= 0:
+            return gs
+        norm = (self.arena.grad.double().pow(2).sum().sqrt() * gs).float()
+        if not bool(torch.isfinite(norm)):
+            self._gn = (float(norm), 0.0)
+            return None
+        coef = torch.clamp(self.clip_grad_norm / (norm + 1e-6), max=1.0)
+        self._gn = (float(norm), float(coef))
+        return float(torch.tensor(gs, dtype=torch.float32) * coef)
+
+    def grad_norm(self) -> Optional[float]:
+        return None if self._gn is None else self._gn[0]
+
+    def clip_coef(self) -> Optional[float]:
+        return None if self._gn is None else self._gn[1]
 
     def _update(self):
         """The native step's three optimizers (elementwise.hip) in torch ops over the arena."""
         p, g, wd = self.arena.data, self.arena.grad, self.weight_decay
+        gs = self._clip()
+        if gs is None:
+            return
         if self.optimizer == "sgd":
             # buf = m * buf + g / W (+ wd * p) ; p -= lr * buf   (torch.optim.SGD semantics, zero-initialised buffer)
             if wd != 0:
-                g = (g * (1.0 / self.world)).add_(p, alpha=wd)
+                g = (g * gs).add_(p, alpha=wd)
                 self.mom.mul_(self.momentum).add_(g)
             else:
-                self.mom.mul_(self.momentum).add_(g, alpha=1.0 / self.world)
+                self.mom.mul_(self.momentum).add_(g, alpha=gs)
             p.add_(self.mom, alpha=-self.lr)
             return
         # torch.optim.Adam / AdamW (no amsgrad), in torch's order of operations
         b1, b2 = self.betas
-        g = g * (1.0 / self.world)
+        g = g * gs
         if self.optimizer == "adamw":
             p.mul_(1.0 - self.lr * wd)
         elif wd != 0:
@@ -208,8 +314,10 @@ def build_trainer(impl="hip", dtype="bf16", device="cuda", world=1, lr=1e-7, bat
                   height=768, width=1024, graph=True, model=None, bucket_mb: float = 25.0,
                   reducer_transport: Optional[str] = None, comm_ctas: Optional[int] = None,
                   graph_bind_inputs: bool = False, graph_max_shapes: int = 8, optimizer: str = "sgd",
-                  momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
-    opt = dict(optimizer=optimizer, momentum=momentum, weight_decay=weight_decay, betas=betas, eps=eps)
+                  momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
+                  accum_steps: int = 1, clip_grad_norm: float = 0.0):
+    opt = dict(optimizer=optimizer, momentum=momentum, weight_decay=weight_decay, betas=betas, eps=eps,
+               accum_steps=accum_steps, clip_grad_norm=clip_grad_norm)
     if impl == "arena":
         return ArenaStepper(device, world=world, lr=lr, model=model, bucket_mb=bucket_mb, **opt)
     if impl == "torch":

@@ -239,14 +239,18 @@ class CANNetExecutor(ContextSchedule):
     def opt_step(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor, lr: float, gscale: float,
                  optimizer: str = "sgd", momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999),
                  eps: float = 1e-8, mom2: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None,
-                 flags: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None):
+                 flags: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None,
+                 gmul: Optional[torch.Tensor] = None):
         """The fused optimizer step for every optimizer (elementwise.hip pack_multi_kernel<DT, OPT>), ONE launch over
         the arena that also writes the 16-bit packs, as ``sgd_step``: ``optimizer`` = "sgd" (torch.optim.SGD with
         momentum and coupled ``weight_decay``; weight decay 0 runs sgd_step's kernel), "adam" (torch.optim.Adam,
         coupled weight decay) or "adamw" (decoupled).  Adam: ``mom`` / ``mom2`` are the first / second moment arenas
         and ``step`` the int32 device count of applied steps, which a one-thread launch after the step advances
-        unless the step was skipped through ``flags``."""
+        unless the step was skipped through ``flags``.  ``gmul``: an fp32 device scalar the kernel multiplies into
+        ``gscale`` (one fp32 product: the clip coefficient of ``grad_norm``)."""
         desc, rows, tiles, goff, boff, voff = self.opt_prepare(data, grad, mom, mom2)
+        if gmul is not None and not (gmul.dtype == torch.float32 and gmul.device == data.device and gmul.numel() >= 1):
+            raise ValueError("opt_step: gmul must be an fp32 tensor on the arena's device")
         if optimizer not in ("sgd", "adam", "adamw"):
             raise ValueError(f"opt_step: unknown optimizer {optimizer!r}")
         adam = optimizer != "sgd"
@@ -259,8 +263,38 @@ class CANNetExecutor(ContextSchedule):
         self.C.opt_pack(desc, rows, tiles, kind, goff, boff, voff, float(lr), float(momentum), float(betas[0]),
                         float(betas[1]), float(eps), float(weight_decay), int(optimizer == "adamw"), float(gscale),
                         step.data_ptr() if adam else 0, flags.data_ptr() if flags is not None else 0,
-                        lr_dev.data_ptr() if lr_dev is not None else 0, self.dt, self._stream())
+                        lr_dev.data_ptr() if lr_dev is not None else 0, self.dt, self._stream(),
+                        gmul.data_ptr() if gmul is not None else 0)
         self._pack_version = self._weights_version()
+
+    def norm_prepare(self, grad: torch.Tensor, slots: Sequence):
+        """The gradient-norm pass's device table and scratch for this gradient arena (elementwise.hip
+        grad_norm_partial_kernel / grad_norm_final_kernel); ``slots``: (element offset, element count) of every
+        parameter in arena order.  Built once: call before a graph capture (the build copies to the device).
+        Returns ``gn``, the fp32 result vector {global norm, clip coefficient, per-parameter norms in slot order}."""
+        if grad.dtype != torch.float32 or not grad.is_contiguous():
+            raise ValueError("norm_prepare: the gradient arena must be contiguous fp32")
+        slots = [(int(o), int(n)) for o, n in slots]
+        if not slots or any(o < 0 or n < 0 or o + n > grad.numel() for o, n in slots):
+            raise ValueError("norm_prepare: every slot must lie inside the gradient arena")
+        dev = grad.device
+        chunk = self.C.grad_norm_chunk()
+        self._norm_max = max(n for _, n in slots)
+        self._norm_np = len(slots)
+        self._norm_tab = torch.tensor(slots, dtype=torch.int64, device=dev)
+        self._norm_part = torch.zeros(len(slots) * max(1, -(-self._norm_max // chunk)), dtype=torch.float64, device=dev)
+        self._norm_grad = grad
+        self.gn = torch.zeros(2 + len(slots), dtype=torch.float32, device=dev)
+        return self.gn
+
+    def grad_norm(self, gscale: float, max_norm: float, flags: Optional[torch.Tensor] = None):
+        """Two launches over the prepared arena: gn[0] = gscale * ||g||, gn[1] = min(1, max_norm / (gn[0] + 1e-6))
+        (``inf``: measure only, exactly 1), gn[2 + i] = gscale * ||g_i||.  A non-finite gradient gives coefficient 0
+        and sets flags[2], which the optimizer kernels skip on."""
+        self.C.grad_norm(self._norm_grad.data_ptr(), self._norm_tab.data_ptr(), self._norm_np, self._norm_max,
+                         self._norm_part.data_ptr(), self.gn.data_ptr(), float(gscale), float(max_norm),
+                         flags.data_ptr() + 8 if flags is not None else 0, self._stream())
+        return self.gn
 
     def opt_prepare(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor,
                     mom2: Optional[torch.Tensor] = None):

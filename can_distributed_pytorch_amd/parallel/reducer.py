@@ -123,6 +123,9 @@ class BucketedReducer:
         self._pending = None
         self._next = 0
         self._works = []
+        # paused: mark_ready is a no-op (gradient accumulation: the autograd hooks of a window's non-closing
+        # micro-steps launch nothing; the closing micro-step all-reduces the accumulated arena once)
+        self.paused = False
         self._timing = False
         self._host_t = None          # torch transport timing: host clock per launched bucket
 
@@ -199,6 +202,8 @@ class BucketedReducer:
         return {"buckets": bk, "backward_end_ms": round(bwd, 4), "exposed_ms": round(max(0.0, last_end - bwd), 4)}
 
     def mark_ready(self, params: Sequence[int]):
+        if self.paused:
+            return
         if self._native is not None:
             from ..ops import _ext
             self._native.mark_ready(list(params), _ext.stream_ptr(self.arena.grad.device))

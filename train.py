@@ -51,6 +51,20 @@ def graph_mode(v):
     return str2bool(v)
 
 
+def accum_count(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"--accum-steps must be >= 1, got {v!r}")
+    return n
+
+
+def clip_norm(v):
+    x = float(v)
+    if not x >= 0:
+        raise argparse.ArgumentTypeError(f"--clip-grad-norm must be >= 0 (0 = off, inf = measure only), got {v!r}")
+    return x
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="CANNet training on MI355X")
     # ---- reference flags (same names / defaults)
@@ -64,6 +78,15 @@ def build_parser():
                         "size for every optimizer (the reference's rule)")
     p.add_argument("--momentum", type=float, default=0.95, help="SGD momentum")
     p.add_argument("--weight-decay", type=float, default=0.0)
+    p.add_argument("--accum-steps", type=accum_count, default=1,
+                   help="gradient accumulation: one optimizer step per window of this many batches, on the SUM of "
+                        "their gradients (the loss is sum-reduced, so a window of k batch-1 steps of any image sizes "
+                        "is one batch-k step of the reference's loss; --lr is NOT rescaled by k).  A window still "
+                        "open at the end of an epoch is closed there")
+    p.add_argument("--clip-grad-norm", type=clip_norm, default=0.0,
+                   help="clip the global 2-norm of the (accumulated, averaged) gradient to this value ahead of the "
+                        "optimizer, torch.nn.utils.clip_grad_norm_'s rule; 0 (default) = off, inf = measure the norm "
+                        "only (logged as grad_norm)")
     p.add_argument("--beta1", type=float, default=0.9, help="Adam / AdamW first-moment decay")
     p.add_argument("--beta2", type=float, default=0.999, help="Adam / AdamW second-moment decay")
     p.add_argument("--eps", type=float, default=1e-8, help="Adam / AdamW epsilon")
@@ -196,7 +219,8 @@ def main(args):
     # combination (--impl torch, and --impl hip --dtype fp32 = Fp32Stepper) is a TorchStepper with a torch optimizer
     native = args.impl == "hip" and args.dtype != "fp32"
     opt = dict(optimizer=args.optimizer, momentum=args.momentum, weight_decay=args.weight_decay,
-               betas=(args.beta1, args.beta2), eps=args.eps)
+               betas=(args.beta1, args.beta2), eps=args.eps, accum_steps=args.accum_steps,
+               clip_grad_norm=args.clip_grad_norm)
     if native:
         stepper = build_trainer(impl="hip", dtype=args.dtype, device=device, world=world, lr=base_lr, graph=graph,
                                 model=model, bucket_mb=args.bucket_mb, comm_ctas=args.comm_ctas,
@@ -239,7 +263,8 @@ def main(args):
             mean_loss = train_one_epoch_native(stepper, train_loader, device, epoch, log=log,
                                                prep=train_prep if raw else prep)
         else:
-            mean_loss = train_one_epoch(net, stepper.opt, train_loader, device, epoch)
+            mean_loss = train_one_epoch(net, stepper.opt, train_loader, device, epoch,
+                                        accum_steps=args.accum_steps, clip_grad_norm=args.clip_grad_norm)
         t_train = time.perf_counter() - t0
         if (epoch + 1) % args.eval_every == 0 or epoch == args.epochs - 1:
             mae_sum = evaluate(net, test_loader, device, epoch, show_images=args.show and rank == 0,
