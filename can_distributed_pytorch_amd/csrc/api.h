@@ -110,6 +110,10 @@ int can_preprocess_image(const void* img, int H0, int W0, int C, int flip, void*
 // one launch per batch: packed uint8 images / fp32 densities, desc [n][8] int64 (device)
 int can_preprocess_batch(const void* imgs, const float* dens, const long long* desc, int n, void* x4, float* gt,
                          int Ho, int Wo, int ds, int dt, void* stream);
+// random-crop batch, one launch, no resize: desc [n][8] int64 = {image byte offset, H0, W0, C, flip, y0, x0, 1} on the
+// device and (desc_host) on the host, where every window is checked against its image and img_bytes before the launch
+int can_preprocess_crop(const void* imgs, long long img_bytes, const long long* desc, const long long* desc_host,
+                        int n, void* x4, int CH, int CW, int ds, int dt, void* stream);
 // synthetic batch: full-res densities [n][H][W] + coarse noise [n][3][H/16][W/16] -> x4 NHWC4, gt [n][H/8][W/8]
 int can_synth_render(const float* dens, const float* noise, float* dmax, void* x4, float* gt, int n, int H, int W,
                      int dt, void* stream);

@@ -126,6 +126,44 @@ __global__ void __launch_bounds__(256) preprocess_batch_kernel(const unsigned ch
   }
 }
 
+// Random-crop batch in ONE launch (no resize): desc[n] = {image byte offset, H0, W0, C, flip, y0, x0, 1}; several
+// descriptors may share one image.  Output sample n = the window [y0, y0+vh) x [x0, x0+vw) of its image, vh =
+// min(CH, H0/ds*ds), vw = min(CW, W0/ds*ds), mirrored within the window when flipped, normalised, zero outside the
+// window (bottom / right padding of an image smaller than the crop).  A thread writes two adjacent NHWC4 pixels as
+// one 16-byte store (CW is even); it reads only bytes of the window.
+template <int DT>
+__global__ void __launch_bounds__(256) preprocess_crop_kernel(const unsigned char* __restrict__ imgs,
+                                                              const long long* __restrict__ desc,
+                                                              uint4* __restrict__ x4, int CH, int CW, int ds) {
+  const long long* d = desc + (size_t)blockIdx.y * 8;
+  const int H0 = (int)d[1], W0 = (int)d[2], C = (int)d[3], flip = (int)d[4], y0 = (int)d[5], x0 = (int)d[6];
+  const int vh = min(CH, H0 / ds * ds), vw = min(CW, W0 / ds * ds);
+  const unsigned char* img = imgs + d[0];
+  const int half = CW / 2;
+  uint4* out = x4 + (size_t)blockIdx.y * CH * half;
+  const float m[3] = {0.485f, 0.456f, 0.406f}, is[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < CH * half; i += gridDim.x * 256) {
+    const int oy = i / half, ox = (i % half) * 2;
+    unsigned int w[4] = {0u, 0u, 0u, 0u};
+    if (oy < vh) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const int x = ox + p;
+        if (x < vw) {
+          const int sx = x0 + (flip ? vw - 1 - x : x);
+          const unsigned char* px = img + ((size_t)(y0 + oy) * W0 + sx) * C;
+          float v[3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) v[c] = ((float)px[(C == 1) ? 0 : c] * (1.f / 255.f) - m[c]) * is[c];
+          w[2 * p] = pack2<DT>(v[0], v[1]);
+          w[2 * p + 1] = pack2<DT>(v[2], 0.f);
+        }
+      }
+    }
+    out[i] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Synthetic crowd batch on the GPU (train.py --synthetic / bench data; data/synthetic.py is the CPU
 // reference of the same recipe): per image, head points (host RNG, tiny) -> fixed-sigma Gaussian
@@ -203,6 +241,31 @@ extern "C" int can_preprocess_batch(const void* imgs, const float* dens, const l
   CAN_LAUNCH_DT(dt, preprocess_batch_kernel, dim3(bx, n, (dens != nullptr && gt != nullptr) ? 2 : 1), dim3(256), 0,
                 (hipStream_t)stream,
                 (const unsigned char*)imgs, dens, desc, (uint2*)x4, gt, Ho, Wo, ds, (float)(ds * ds));
+  return (int)hipGetLastError();
+}
+
+// desc: the device copy the kernel reads; desc_host: the same [n][8] table on the host, checked here before the
+// launch (a window that leaves its image, or an image that leaves the img_bytes of packed images, is refused).
+extern "C" int can_preprocess_crop(const void* imgs, long long img_bytes, const long long* desc,
+                                   const long long* desc_host, int n, void* x4, int CH, int CW, int ds, int dt,
+                                   void* stream) {
+  using namespace can;
+  if (n <= 0 || n > 65535 || ds <= 0 || CH <= 0 || CW <= 0 || CH % ds || CW % ds || CW % 2) return -2;
+  if ((long long)CH * CW > 0x7fffffff) return -2;
+  if (imgs == nullptr || desc == nullptr || desc_host == nullptr || x4 == nullptr || ((uintptr_t)x4 & 15)) return -2;
+  for (int i = 0; i < n; ++i) {
+    const long long* d = desc_host + (size_t)i * 8;
+    const long long off = d[0], H0 = d[1], W0 = d[2], C = d[3], flip = d[4], y0 = d[5], x0 = d[6];
+    if (d[7] != 1 || (C != 1 && C != 3 && C != 4) || (flip != 0 && flip != 1)) return -2;
+    if (H0 <= 0 || W0 <= 0 || H0 > 0x7fffffff || W0 > 0x7fffffff) return -2;
+    if (off < 0 || off > img_bytes || H0 * W0 > (img_bytes - off) / C) return -2;
+    const long long vh = H0 / ds * ds < CH ? H0 / ds * ds : CH, vw = W0 / ds * ds < CW ? W0 / ds * ds : CW;
+    if (y0 < 0 || x0 < 0 || y0 > H0 - vh || x0 > W0 - vw) return -2;
+  }
+  int bx = (CH * (CW / 2) + 255) / 256;
+  if (bx > 512) bx = 512;
+  CAN_LAUNCH_DT(dt, preprocess_crop_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream,
+                (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW, ds);
   return (int)hipGetLastError();
 }
 

@@ -14,6 +14,10 @@ DataLoader workers cannot replay one another's stream (a ``random.Random``
 pickled into every worker would), and a resumed run draws exactly the flips
 of an uninterrupted one.  The epoch comes from ``set_epoch`` or, with
 worker processes, travels with the index (``EpochTaggedSampler``).
+``crop=(ch, cw)`` (train phase only) turns an item into ``crops_per_image``
+random windows of that size of the one decoded image, each with its own
+offset and flip drawn by ``crop_draw`` from (seed, epoch, index, k), zero-padded
+where the image is smaller than the crop (README, "Random-crop training").
 ``SyntheticCrowdDataset`` provides the same item contract without files
 (benchmarks, tests, smoke runs).
 """
@@ -42,6 +46,37 @@ def _splitmix64(x: int) -> int:
 def flip_draw(seed: int, epoch: int, index: int) -> bool:
     """The p=0.5 horizontal flip of sample ``index`` in ``epoch`` (stateless, worker-independent)."""
     return bool(_splitmix64(_splitmix64(_splitmix64(seed & _M64) ^ (epoch & _M64)) ^ (index & _M64)) >> 63)
+
+
+def crop_window(h0: int, w0: int, ch: int, cw: int, downsample: int = 8):
+    """(vh, vw): the extent of a (ch, cw) crop inside an h0 x w0 image -- the crop itself, or the image's largest
+    multiple of the downsample where the image is smaller (the rest of the crop is zero padding)."""
+    return min(ch, h0 // downsample * downsample), min(cw, w0 // downsample * downsample)
+
+
+def crop_draw(seed: int, epoch: int, index: int, k: int, ny: int, nx: int):
+    """Crop ``k`` of sample ``index`` in ``epoch``: (y0 uniform on [0, ny), x0 uniform on [0, nx), p=0.5 flip).
+    Stateless like ``flip_draw`` (one splitmix64 chain over seed, epoch, index, k, then one hash per drawn value),
+    so it depends neither on a worker's history nor on how many crops an image yields."""
+    s = _splitmix64(_splitmix64(_splitmix64(_splitmix64(seed & _M64) ^ (epoch & _M64)) ^ (index & _M64)) ^ (k & _M64))
+    y0 = (_splitmix64(s ^ 1) * max(1, int(ny))) >> 64          # multiply-shift: bias < n / 2^64
+    x0 = (_splitmix64(s ^ 2) * max(1, int(nx))) >> 64
+    return int(y0), int(x0), bool(_splitmix64(s ^ 3) >> 63)
+
+
+def _pad_to(a: np.ndarray, h: int, w: int) -> np.ndarray:
+    """Zero-pad the last two axes at the bottom / right to (h, w)."""
+    if a.shape[-2:] == (h, w):
+        return a
+    out = np.zeros(a.shape[:-2] + (h, w), dtype=a.dtype)
+    out[..., :a.shape[-2], :a.shape[-1]] = a
+    return out
+
+
+def crop_collate(batch):
+    """collate_fn for CrowdDataset(crop=..., raw=False): the K-stacks of a batch, concatenated to [B*K, ...]."""
+    imgs, gts = zip(*batch)
+    return torch.cat(imgs), torch.cat(gts)
 
 
 def density_to_gt(dmap: np.ndarray, h: int, w: int, downsample: int, flip: bool) -> np.ndarray:
@@ -102,7 +137,7 @@ def imread(path: str) -> np.ndarray:
 
 class CrowdDataset(Dataset):
     def __init__(self, img_root: str, gt_dmap_root: str, gt_downsample: int = 1, phase: str = "train",
-                 seed: Optional[int] = None, raw: bool = False):
+                 seed: Optional[int] = None, raw: bool = False, crop=None, crops_per_image: int = 1):
         self.img_root = img_root
         self.gt_dmap_root = gt_dmap_root
         self.gt_downsample = max(1, int(gt_downsample))
@@ -115,6 +150,17 @@ class CrowdDataset(Dataset):
         # raw=True: return (uint8 image, full-res density, flip) and let the GPU
         # preprocess it (ops/preprocess.py) instead of resizing on the CPU
         self.raw = raw
+        # crop=(ch, cw): a train item is crops_per_image random windows of that size of ONE decoded image (each with
+        # its own offset and flip, crop_draw), zero-padded where the image is smaller; test items stay whole images
+        self.crop = None
+        self.crops_per_image = int(crops_per_image)
+        if crop is not None and phase == "train":
+            ch, cw = (int(v) for v in crop)
+            if ch <= 0 or cw <= 0 or ch % self.gt_downsample or cw % self.gt_downsample:
+                raise ValueError(f"crop {ch}x{cw} must be a positive multiple of the downsample {self.gt_downsample}")
+            if self.crops_per_image < 1:
+                raise ValueError(f"crops_per_image must be >= 1, got {crops_per_image}")
+            self.crop = (ch, cw)
 
     def __len__(self):
         return self.n_samples
@@ -134,6 +180,8 @@ class CrowdDataset(Dataset):
             raise IndexError("index range error")
         name = self.img_names[index]
         img = imread(os.path.join(self.img_root, name))
+        if self.crop is not None:
+            return self._crop_item(img, name, epoch, index)
         flip = self.phase == "train" and flip_draw(self.seed, epoch, index)
         if self.raw:
             # the GPU resizes / normalises the image; the ground truth is brought to its 1/d resolution here,
@@ -148,6 +196,34 @@ class CrowdDataset(Dataset):
         dmap = np.load(self.gt_path(name))                       # allow_pickle=False (default)
         im, dm = prepare_pair(img, dmap, self.gt_downsample, flip)
         return torch.from_numpy(np.ascontiguousarray(im)), torch.from_numpy(np.ascontiguousarray(dm))
+
+
+    def _crop_item(self, img: np.ndarray, name: str, epoch: int, index: int):
+        """K crops of one decoded image.  raw=False: ([K,3,ch,cw] f32, [K,1,ch/d,cw/d] f32), each prepare_pair of the
+        window's slices, zero-padded.  raw=True: (uint8 image, [K,1,ch/d,cw/d] f32, int64 [K,3] of (y0, x0, flip)):
+        the GPU cuts the windows (ops/preprocess.py), the ground truths are made here from the memory-mapped map."""
+        d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
+        h0, w0 = img.shape[:2]
+        dmap = np.load(self.gt_path(name), mmap_mode="r" if self.raw else None)      # allow_pickle=False (default)
+        if tuple(dmap.shape) != (h0, w0):
+            raise ValueError(f"{name}: density map {tuple(dmap.shape)} differs from its image {(h0, w0)}: a crop "
+                             "takes the same window of both")
+        vh, vw = crop_window(h0, w0, ch, cw, d)
+        draws = [crop_draw(self.seed, epoch, index, k, h0 - vh + 1, w0 - vw + 1) for k in range(K)]
+        if self.raw:
+            if img.dtype != np.uint8:
+                img = np.clip(np.asarray(img, dtype=np.float64) * (255.0 if img.dtype.kind == "f" else 1.0),
+                              0, 255).astype(np.uint8)
+            gts = np.stack([_pad_to(density_to_gt(dmap[y0:y0 + vh, x0:x0 + vw], vh, vw, d, fl), ch // d, cw // d)
+                            for y0, x0, fl in draws])
+            wins = torch.tensor([[y0, x0, int(fl)] for y0, x0, fl in draws], dtype=torch.int64)
+            return torch.from_numpy(np.require(img, requirements=("C", "W"))), torch.from_numpy(gts), wins
+        ims, dms = [], []
+        for y0, x0, fl in draws:
+            im, dm = prepare_pair(img[y0:y0 + vh, x0:x0 + vw], dmap[y0:y0 + vh, x0:x0 + vw], d, fl)
+            ims.append(_pad_to(im, ch, cw))
+            dms.append(_pad_to(dm, ch // d, cw // d))
+        return torch.from_numpy(np.stack(ims)), torch.from_numpy(np.stack(dms))
 
 
 class SyntheticCrowdDataset(Dataset):

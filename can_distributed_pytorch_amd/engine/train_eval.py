@@ -106,6 +106,7 @@ def train_one_epoch_native(stepper, train_loader, device, epoch, log=None, log_e
     first = next(it, None) if ahead else None                # (an empty loader: nothing to issue)
     pending = prep.issue(first) if first is not None else None
     clip = getattr(stepper, "clip_grad_norm", 0.0) > 0
+    last_loss = None                                         # the latest closed window's loss (for the records)
 
     def add(loss):
         # a window's loss arrives on the call that closes it (None on the others); the running mean stays "sum of
@@ -127,6 +128,8 @@ def train_one_epoch_native(stepper, train_loader, device, epoch, log=None, log_e
             img, gt = prep(batch) if prep is not None else batch
             loss = stepper.step(img, gt)      # SUM of the per-rank losses (averaged below)
         add(loss)
+        if loss is not None:
+            last_loss = loss
         n += 1
         imgs += img.shape[0] * get_world_size()
         # NHWC4 (GPU-preprocessed) or NCHW input: per-pixel throughput for variable-size images
@@ -142,7 +145,9 @@ def train_one_epoch_native(stepper, train_loader, device, epoch, log=None, log_e
                     loader.desc = f"[epoch {epoch}] mean loss {round(ml, 3)}"
                 if log is not None:
                     dt = time.perf_counter() - t0
-                    rec = dict(kind="train", epoch=epoch, step=step + 1, mean_loss=ml, imgs_per_s=imgs / max(dt, 1e-9))
+                    rec = dict(kind="train", epoch=epoch, step=step + 1, mean_loss=ml, imgs_per_s=imgs / max(dt, 1e-9),
+                               input_shape=list(img.shape),
+                               loss=None if last_loss is None else float(last_loss) / max(1, get_world_size()))
                     if clip:
                         rec.update(grad_norm=stepper.grad_norm(), clip_coef=stepper.clip_coef())
                     log.log(**rec)

@@ -9,6 +9,8 @@ Per batch: the DataLoader worker packs the decoded samples back to back
 in ONE uint8 buffer), the main process makes one pinned H2D copy of it and
 ONE kernel launch turns the batch into network inputs (``preprocess_packed``).
 ``preprocess_batch`` is the per-sample form (tests / variable-size use).
+``PackedCollate(crop=(ch, cw))`` packs random-crop batches: every image once,
+one descriptor per crop, cut on the GPU by one launch of the crop kernel.
 """
 from __future__ import annotations
 
@@ -68,12 +70,53 @@ class PackedCollate:
     desc_offset (16-byte aligned), desc[i] = (image byte offset, H0, W0, C, flip, 0, 0, 0).  The raw dataset already
     brought each ground truth to 1/d resolution (flip and x d^2 included), so only the images are resized on the
     GPU.  Runs in the loader workers; pin_memory=True pins the buffer.  (Three separate pinned copies per batch were
-    ~0.23 ms of host time per step at batch 1: profiles/r5/host/.)"""
+    ~0.23 ms of host time per step at batch 1: profiles/r5/host/.)  crop=(ch, cw): the random-crop form for
+    CrowdDataset(raw=True, crop=...) items, see ``_call_crop``."""
 
-    def __init__(self, downsample: int = 8):
+    def __init__(self, downsample: int = 8, crop=None):
         self.ds = downsample
+        self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
+        if self.crop is not None and (min(self.crop) <= 0 or self.crop[0] % downsample or self.crop[1] % downsample):
+            raise ValueError(f"crop {self.crop} must be a positive multiple of the downsample {downsample}")
+
+    def _call_crop(self, batch: List):
+        """CrowdDataset(raw=True, crop=...) items (uint8 image, gts [K,1,ch/d,cw/d], windows [K,3] of (y0, x0, flip)):
+        every image's bytes ONCE, the [B*K,1,ch/d,cw/d] ground truth and one descriptor per output sample,
+        desc = (image byte offset, H0, W0, C, flip, y0, x0, 1) -- the K crops of an image share its offset.  The
+        meta tuple gains a sixth field, the number of images, which marks the pack as cropped."""
+        ch, cw = self.crop
+        imgs, gts, wins = zip(*batch)
+        rows, ioff = [], 0
+        for im, g, wn in zip(imgs, gts, wins):
+            hh, ww = im.shape[:2]
+            c = 1 if im.dim() == 2 else im.shape[2]
+            if g.dim() != 4 or tuple(g.shape[1:]) != (1, ch // self.ds, cw // self.ds) or \
+                    tuple(wn.shape) != (g.shape[0], 3):
+                raise ValueError("cropped raw samples must carry ground truths [K, 1, ch/d, cw/d] and windows [K, 3]")
+            rows += [[ioff, hh, ww, c, fl, y0, x0, 1] for y0, x0, fl in wn.tolist()]
+            ioff += hh * ww * c
+        desc = torch.tensor(rows, dtype=torch.int64)
+        buf, goff, doff = self._fill(imgs, ioff, torch.cat(gts).float().contiguous(), desc)
+        return buf, (desc.shape[0], ch, cw, goff, doff, len(imgs))
+
+    @staticmethod
+    def _fill(imgs, ioff, gt, desc):
+        """One buffer: the images back to back | the ground truth at goff | the descriptors at doff (16-byte aligned)."""
+        goff = -(-ioff // 16) * 16
+        doff = -(-(goff + 4 * gt.numel()) // 16) * 16
+        buf = torch.empty(doff + 8 * desc.numel(), dtype=torch.uint8)
+        o = 0
+        for im in imgs:
+            k = im.numel()
+            buf[o:o + k] = im.reshape(-1)
+            o += k
+        buf[goff:goff + 4 * gt.numel()] = gt.reshape(-1).view(torch.uint8)
+        buf[doff:] = desc.reshape(-1).view(torch.uint8)
+        return buf, goff, doff
 
     def __call__(self, batch: List):
+        if self.crop is not None:
+            return self._call_crop(batch)
         imgs, gts, flips = zip(*batch)
         h0, w0 = imgs[0].shape[:2]
         ho, wo = (h0 // self.ds) * self.ds, (w0 // self.ds) * self.ds
@@ -88,18 +131,19 @@ class PackedCollate:
             ch = 1 if im.dim() == 2 else im.shape[2]
             desc[i] = torch.tensor([ioff, hh, ww, ch, int(bool(fl)), 0, 0, 0])
             ioff += hh * ww * ch
-        gt = torch.stack(gts).float().contiguous()
-        goff = -(-ioff // 16) * 16
-        doff = -(-(goff + 4 * gt.numel()) // 16) * 16
-        buf = torch.empty(doff + 8 * desc.numel(), dtype=torch.uint8)
-        o = 0
-        for im in imgs:
-            k = im.numel()
-            buf[o:o + k] = im.reshape(-1)
-            o += k
-        buf[goff:goff + 4 * gt.numel()] = gt.reshape(-1).view(torch.uint8)
-        buf[doff:] = desc.reshape(-1).view(torch.uint8)
+        buf, goff, doff = self._fill(imgs, ioff, torch.stack(gts).float().contiguous(), desc)
         return buf, (len(imgs), ho, wo, goff, doff)
+
+
+def _unpack(packed):
+    """(buf, (n, Ho, Wo, gt_offset, desc_offset), cropped) of a PackedCollate output; a cropped pack's meta tuple
+    carries a sixth field (its number of images) and n counts output samples, one descriptor each."""
+    buf, meta = packed
+    n, ho, wo, goff, doff = meta[:5]
+    if len(meta) not in (5, 6) or buf.dtype != torch.uint8 or buf.dim() != 1 or goff % 16 or doff % 16 or \
+            buf.numel() != doff + 64 * n:
+        raise ValueError("packed batch: one uint8 buffer (images | fp32 ground truth | int64 descriptors)")
+    return buf, (n, ho, wo, goff, doff), len(meta) == 6
 
 
 def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = torch.bfloat16,
@@ -109,9 +153,7 @@ def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = 
     compute stream then waits for it): a pinned copy queued behind the previous step's kernels on the compute stream
     held the host ~0.6 ms per step at batch 1 (profiles/r5/host/), one on an idle copy stream does not."""
     C = _ext.require()
-    buf, (n, ho, wo, goff, doff) = packed
-    if buf.dtype != torch.uint8 or buf.dim() != 1 or goff % 16 or doff % 16 or buf.numel() != doff + 64 * n:
-        raise ValueError("packed batch: one uint8 buffer (images | fp32 ground truth | int64 descriptors)")
+    buf, (n, ho, wo, goff, doff), cropped = _unpack(packed)
     dev = torch.device(device)
     from .conv import dt_code
     if copy_stream is not None:
@@ -127,8 +169,12 @@ def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = 
     gtd = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
     ds = d[doff:].view(torch.int64).view(n, 8)
     x4 = torch.empty(n, ho, wo, 4, dtype=dtype, device=dev)
-    C.preprocess_batch(ib.data_ptr(), 0, ds.data_ptr(), n, x4.data_ptr(), 0, ho, wo, downsample, dt_code(dtype),
-                       _ext.stream_ptr(dev))
+    if cropped:
+        C.preprocess_crop(ib.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), ho, wo,
+                          downsample, dt_code(dtype), _ext.stream_ptr(dev))
+    else:
+        C.preprocess_batch(ib.data_ptr(), 0, ds.data_ptr(), n, x4.data_ptr(), 0, ho, wo, downsample, dt_code(dtype),
+                           _ext.stream_ptr(dev))
     return x4, gtd
 
 
@@ -151,9 +197,7 @@ class AheadPrep:
     def issue(self, packed):
         from .conv import dt_code
         C = _ext.require()
-        buf, (n, ho, wo, goff, doff) = packed
-        if buf.dtype != torch.uint8 or buf.dim() != 1 or goff % 16 or doff % 16 or buf.numel() != doff + 64 * n:
-            raise ValueError("packed batch: one uint8 buffer (images | fp32 ground truth | int64 descriptors)")
+        buf, (n, ho, wo, goff, doff), cropped = _unpack(packed)
         # the copy stream must not overwrite memory the compute stream's queued kernels may still read: wait for
         # what the compute stream has queued so far is NOT needed (fresh blocks of the copy stream's own pool), and
         # the hand-off below keeps the blocks out of that pool until the compute stream is done with them
@@ -164,8 +208,12 @@ class AheadPrep:
             ds = d[doff:].view(torch.int64).view(n, 8)
             x4 = torch.empty(n, ho, wo, 4, dtype=self.dtype, device=self.device)
             with _ext.launch_on(self.copy.cuda_stream):
-                C.preprocess_batch(d.data_ptr(), 0, ds.data_ptr(), n, x4.data_ptr(), 0, ho, wo, self.ds,
-                                   dt_code(self.dtype), _ext.stream_ptr(self.device))
+                if cropped:
+                    C.preprocess_crop(d.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), ho,
+                                      wo, self.ds, dt_code(self.dtype), _ext.stream_ptr(self.device))
+                else:
+                    C.preprocess_batch(d.data_ptr(), 0, ds.data_ptr(), n, x4.data_ptr(), 0, ho, wo, self.ds,
+                                       dt_code(self.dtype), _ext.stream_ptr(self.device))
             ev = torch.cuda.Event()
             ev.record(self.copy)
         return x4, gt, d, ev

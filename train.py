@@ -65,8 +65,33 @@ def clip_norm(v):
     return x
 
 
+def crop_size(v):
+    try:
+        h, w = (int(x) for x in str(v).lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--crop-size expects HxW, got {v!r}")
+    if h <= 0 or w <= 0 or h % 8 or w % 8:
+        raise argparse.ArgumentTypeError(f"--crop-size must be positive multiples of 8 (the density downsample), got {v!r}")
+    return h, w
+
+
+def crop_count(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"--crops-per-image must be >= 1, got {v!r}")
+    return n
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.crop_size is not None and ns.synthetic:
+            self.error("--crop-size crops decoded dataset images; it cannot be combined with --synthetic")
+        return ns
+
+
 def build_parser():
-    p = argparse.ArgumentParser(description="CANNet training on MI355X")
+    p = _Parser(description="CANNet training on MI355X")
     # ---- reference flags (same names / defaults)
     p.add_argument("--epochs", type=int, default=500)
     p.add_argument("--batch-size", type=int, default=1)
@@ -131,6 +156,18 @@ def build_parser():
                    help="make_layers(batch_norm=True) variant (reference C04 branch; stock autograd path only)")
     p.add_argument("--gpu-preprocess", type=str2bool, default=True,
                    help="decode on CPU workers, resize/flip/normalise on the GPU (hip impl, real data)")
+    p.add_argument("--crop-size", type=crop_size, default=None, metavar="HxW",
+                   help="train on random HxW crops (multiples of 8) instead of whole images: any integer offset, a "
+                        "p=0.5 flip per crop, an image smaller than the crop is zero-padded at the bottom / right "
+                        "(the padding takes part in the loss).  Every training batch then has one shape, so "
+                        "--batch-size > 1 works on a mixed-size dataset; evaluation stays on whole images at batch 1.  "
+                        "Default: off")
+    p.add_argument("--crops-per-image", type=crop_count, default=1,
+                   help="with --crop-size: crops cut from every decoded image (one decode, one copy); a step sees "
+                        "batch-size x this many samples and the loss is sum-reduced, so choose --lr as for that many "
+                        "images (as with --accum-steps)")
+    p.add_argument("--log-every", type=int, default=20,
+                   help="steps between the training records of --log-jsonl (each reads the loss back: a host sync)")
     return p
 
 
@@ -143,6 +180,12 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
     from can_distributed_pytorch_amd.data.dataset import EpochTaggedSampler
     from can_distributed_pytorch_amd.ops.preprocess import PackedCollate
     collate = PackedCollate() if raw else None
+    crop = args.crop_size
+    train_collate, eval_batch = collate, args.batch_size
+    if crop is not None:
+        # every training sample is a crop of one size; test images stay whole and of mixed size: batch 1
+        from can_distributed_pytorch_amd.data.dataset import crop_collate
+        train_collate, eval_batch = (PackedCollate(crop=crop) if raw else crop_collate), 1
     if args.synthetic:
         h, w = (int(v) for v in args.synthetic.lower().split("x"))
         train_ds = SyntheticCrowdDataset(args.synthetic_n, h, w, seed=args.seed)
@@ -150,7 +193,8 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
     else:
         r = args.data_root
         train_ds = CrowdDataset(os.path.join(r, "train_data", "images"), os.path.join(r, "train_data", "ground_truth"),
-                                gt_downsample=8, phase="train", seed=args.seed, raw=raw)
+                                gt_downsample=8, phase="train", seed=args.seed, raw=raw, crop=crop,
+                                crops_per_image=args.crops_per_image if crop is not None else 1)
         test_ds = CrowdDataset(os.path.join(r, "test_data", "images"), os.path.join(r, "test_data", "ground_truth"),
                                gt_downsample=8, phase="test", raw=raw)
     train_sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed)
@@ -166,9 +210,9 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
         return train_loader, test_loader, train_sampler, test_sampler
     pin = torch.cuda.is_available()
     train_loader = DataLoader(train_ds, batch_sampler=bs, num_workers=args.num_workers, pin_memory=pin,
-                              persistent_workers=args.num_workers > 0, collate_fn=collate,
+                              persistent_workers=args.num_workers > 0, collate_fn=train_collate,
                               prefetch_factor=4 if args.num_workers > 0 else None)
-    test_loader = DataLoader(test_ds, sampler=test_sampler, batch_size=args.batch_size, num_workers=args.num_workers,
+    test_loader = DataLoader(test_ds, sampler=test_sampler, batch_size=eval_batch, num_workers=args.num_workers,
                              pin_memory=pin, shuffle=False, collate_fn=collate)
     return train_loader, test_loader, train_sampler, test_sampler
 
@@ -261,7 +305,7 @@ def main(args):
         t0 = time.perf_counter()
         if native:
             mean_loss = train_one_epoch_native(stepper, train_loader, device, epoch, log=log,
-                                               prep=train_prep if raw else prep)
+                                               log_every=max(1, args.log_every), prep=train_prep if raw else prep)
         else:
             mean_loss = train_one_epoch(net, stepper.opt, train_loader, device, epoch,
                                         accum_steps=args.accum_steps, clip_grad_norm=args.clip_grad_norm)
@@ -288,13 +332,16 @@ def main(args):
                              stepper_state=stepper.resume_state() if native else None, momentum2=momentum2,
                              optimizer_name=args.optimizer)
             lr_now = stepper.lr if native else stepper.opt.param_groups[0]["lr"]
-            ips = len(train_loader) * args.batch_size * world / max(t_train, 1e-9)
+            per_item = args.crops_per_image if args.crop_size is not None else 1
+            ips = len(train_loader) * args.batch_size * per_item * world / max(t_train, 1e-9)
             print(f"[epoch {epoch}] loss: {mean_loss:.4f} mae: {mean_mae:.3f}, min_mae: {min_mae:.3f}, "
                   f"min_epoch: {min_epoch}, train img/s {ips:.1f}")
             st = getattr(stepper, "last_epoch_stats", None) or {}
             log.log(kind="epoch", epoch=epoch, loss=mean_loss, mae=mean_mae, min_mae=min_mae, lr=lr_now,
                     train_imgs_per_s=ips, train_s=t_train, train_mpix_per_s=st.get("mpix_per_s"),
-                    train_loop_imgs_per_s=st.get("imgs_per_s"), batch_size=args.batch_size, world=world)
+                    train_loop_imgs_per_s=st.get("imgs_per_s"), batch_size=args.batch_size, world=world,
+                    **(dict(crop_size=list(args.crop_size), crops_per_image=args.crops_per_image,
+                            eval_batch_size=test_loader.batch_size) if args.crop_size is not None else {}))
             if use_wandb:
                 wandb_log(loss=mean_loss, mae=mean_mae, lr=lr_now)
         barrier()
