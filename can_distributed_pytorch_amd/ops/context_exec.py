@@ -8,8 +8,8 @@ Two forms, picked per map by ``_ctx_linear``:
     output columns (conv_igemm.hip EPI_CTXF: the epilogue upsamples the S x S cell tables, applies the sigmoid, forms
     fi and writes fv | fi into the concat buffer), one GEMM back (EPI_CTXB), fp32 cell GEMMs (ctx_gemm) for the
     50 pooled cells; the expanded maps c_S and their sigmoid maps never exist;
-  * direct (maps narrower than 64 columns at 1/8 resolution, or dispatch ctx_linear = 0): expand the four c_S maps,
-    four sigmoid GEMMs in one batched launch, fuse.
+  * direct (maps narrower than 64 columns or of fewer than 3 rows at 1/8 resolution, or dispatch ctx_linear = 0):
+    expand the four c_S maps, four sigmoid GEMMs in one batched launch, fuse.
 
 ``ContextSchedule`` is a mixin of ops.executor.CANNetExecutor (it uses the executor's packs, streams and side-stream
 fork helpers).
@@ -28,7 +28,8 @@ class ContextSchedule:
     @staticmethod
     def _ctx_linear(fv) -> bool:
         """The context module as one GEMM each way (conv_igemm.hip "Linearised context module"); dispatch ctx_linear =
-        0 or a map narrower than 64 columns: the direct per-scale form (expand -> 4 sigmoid GEMMs -> fuse)."""
+        0, a map narrower than 64 columns or one of fewer than 3 rows: the direct per-scale form (expand -> 4 sigmoid
+        GEMMs -> fuse)."""
         return bool(dispatch.current().ctx_linear) and C.ctx_linear_ok(fv)
 
     def _context_fwd(self, fv, save, wv=None):

@@ -599,8 +599,10 @@ def conv_dgrad_w1g(dy: torch.Tensor, wpack: torch.Tensor, mask: Optional[torch.T
 # Linearised context module (csrc/conv_igemm.hip "Linearised context module", csrc/context.hip ctx_bwd_lin)
 # ---------------------------------------------------------------------------------------------------------------------
 def ctx_linear_ok(fv: torch.Tensor) -> bool:
-    """The one-GEMM context module needs 256-channel tiles and a 256-pixel tile spanning <= 5 image rows (W >= 64)."""
-    return fv.dim() == 4 and fv.shape[-1] % 256 == 0 and fv.shape[2] >= 64
+    """The one-GEMM context module needs 256-channel tiles, a 256-pixel tile spanning <= 5 image rows (W >= 64) and
+    at least 3 rows: the backward epilogue's pooling adjoint adds at most two row bins per scale at a pixel
+    (conv_igemm.hip ctx_pool_cols), and below 3 rows the bins of the 3- and 6-grids repeat (up to 6 hold one pixel)."""
+    return fv.dim() == 4 and fv.shape[-1] % 256 == 0 and fv.shape[2] >= 64 and fv.shape[1] >= 3
 
 
 def _check_cells(t: torch.Tensor, n: int, c: int, name: str):
@@ -616,7 +618,7 @@ def conv_ctx_fwd(fv: torch.Tensor, wcat: torch.Tensor, t: torch.Tensor, u: torch
     _check_act(fv, "fv")
     n, h, w, c = fv.shape
     if not ctx_linear_ok(fv):
-        raise ValueError("conv_ctx_fwd needs C % 256 == 0 and w >= 64")
+        raise ValueError("conv_ctx_fwd needs C % 256 == 0, w >= 64 and h >= 3")
     if wcat.dtype != fv.dtype or not wcat.is_contiguous() or tuple(wcat.shape) != (4 * c, c):
         raise ValueError(f"wcat must be a contiguous {fv.dtype} [{4 * c}, {c}] pack")
     _check_cells(t, n, c, "t")
@@ -656,7 +658,7 @@ def conv_ctx_bwd(dg: torch.Tensor, wcat_dgr: torch.Tensor, dave: torch.Tensor, d
     _check_act(fv, "fv")
     n, h, w, c = fv.shape
     if not ctx_linear_ok(fv):
-        raise ValueError("conv_ctx_bwd needs C % 256 == 0 and w >= 64")
+        raise ValueError("conv_ctx_bwd needs C % 256 == 0, w >= 64 and h >= 3")
     _check_act(dg, "dg", 4 * c, dtype=fv.dtype)
     _check_act(dcat, "dcat", 2 * c, dtype=fv.dtype)
     if tuple(dg.shape[:3]) != (n, h, w) or tuple(dcat.shape[:3]) != (n, h, w):

@@ -318,11 +318,13 @@ class CANNetExecutor(ContextSchedule):
 
     PAD_ALIGN = 64
 
-    def padded_width(self, w: int) -> int:
-        """Row pitch the executor runs an input of width w at (see "Ragged widths"): w rounded up to a multiple of 64
-        when w is not one (dispatch pad_width, linearised context module), else w."""
+    def padded_width(self, w: int, h: Optional[int] = None) -> int:
+        """Row pitch the executor runs an input of width w (and height h, when given) at (see "Ragged widths"): w
+        rounded up to a multiple of 64 when w is not one (dispatch pad_width, linearised context module), else w.
+        An input of fewer than 24 rows is never padded: its 1/8-resolution map has fewer than 3 rows and runs the
+        direct context module (ops.conv.ctx_linear_ok), which takes no padded map."""
         d = dispatch.current()
-        if not d.pad_width or w % self.PAD_ALIGN == 0 or not d.ctx_linear:
+        if not d.pad_width or w % self.PAD_ALIGN == 0 or not d.ctx_linear or (h is not None and h < 24):
             return w
         wp = -(-w // self.PAD_ALIGN) * self.PAD_ALIGN
         return wp if wp // 8 >= 64 else w      # the linear context GEMM needs a 1/8-resolution pitch >= 64
@@ -339,7 +341,7 @@ class CANNetExecutor(ContextSchedule):
                 self._w1g_slabs(self.head.weight.device)
             return self.ws
         need = 0
-        hh, ww = h, self.padded_width(w)
+        hh, ww = h, self.padded_width(w, h)
         for s in self.front:
             _, _, _, nd = self.ws.plan(n * hh * ww, 4 if s.first else s.cin, s.cout, 3, s.first, 1, ww)
             need = max(need, nd)
@@ -431,7 +433,7 @@ class CANNetExecutor(ContextSchedule):
     def _pad(self, x):
         """(x at the padded row pitch, valid width or None) for an NHWC4 input (see "Ragged widths")."""
         n, h, w, c = x.shape
-        wp = self.padded_width(w)
+        wp = self.padded_width(w, h)
         if wp == w:
             return x, None
         xp = torch.zeros(n, h, wp, c, dtype=x.dtype, device=x.device)

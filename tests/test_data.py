@@ -197,5 +197,7 @@ def test_executor_padded_width_rule():
     for w, wp in cases.items():
         assert ex.padded_width(w) == wp, (w, ex.padded_width(w), wp)
         assert wp % 8 == 0 and (wp == w or (wp % 64 == 0 and wp // 8 >= 64))
+    # a map of fewer than 3 rows runs the direct context module (ops.conv.ctx_linear_ok), which takes no padded map
+    assert ex.padded_width(1016, 16) == 1016 and ex.padded_width(1016, 24) == 1024
     with dispatch.override(pad_width=0):
         assert all(ex.padded_width(w) == w for w in cases)
