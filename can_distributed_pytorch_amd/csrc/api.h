@@ -72,6 +72,15 @@ int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long l
                  long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
                  int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt, void* stream,
                  const float* gmul);
+// EMA of the parameters: fused into the optimizer launch (eoff: the EMA arena's offset from the masters in floats,
+// ema_t: device count of applied updates), the stand-alone update, and the master <-> EMA swap launch
+int can_opt_pack_ema(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
+                     long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
+                     int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt, void* stream,
+                     const float* gmul, long long eoff, double ema_decay, int ema_warmup, int* ema_t);
+int can_ema(float* e, const float* p, size_t n, double decay, int warmup, int step, int* t_dev, float* flags,
+            void* stream);
+int can_swap_pack(const long long* desc, int rows, int max_tiles, long long eoff, int dt, void* stream);
 // gradient-norm pass over the fp32 arena (two launches, fixed order) and the accumulation window's loss tick
 int can_grad_norm_chunk();
 int can_grad_norm(const float* g, const long long* tab, int np, long long max_count, double* part, float* gn,

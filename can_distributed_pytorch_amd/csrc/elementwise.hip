@@ -416,7 +416,9 @@ constexpr int kPackRow = 12;
 // OPT: which optimizer runs in front of the packing.  OPT_SGD is the step above (weight decay 0); OPT_SGD_WD adds
 // torch.optim.SGD's coupled weight decay (g += wd * p ahead of the momentum); OPT_ADAM is torch.optim.Adam / AdamW
 // (adam1 below), its second moment in a third arena voff floats from the masters.
-enum { OPT_NONE = 0, OPT_SGD = 1, OPT_SGD_WD = 2, OPT_ADAM = 3 };
+// OPT_SWAP is no optimizer: it exchanges every master with its EMA copy (eoff floats away) and packs what lands in the
+// master slot (evaluation under the averaged weights, see ema below).
+enum { OPT_NONE = 0, OPT_SGD = 1, OPT_SGD_WD = 2, OPT_ADAM = 3, OPT_SWAP = 4 };
 struct OptArgs {
   long long goff, boff, voff;  // gradient / momentum (Adam: first moment) / second-moment arena offsets, in floats
   float lr, momentum, gscale;
@@ -428,7 +430,11 @@ struct OptArgs {
   const int* t;                // Adam: applied steps so far, on the device (advanced by opt_tick_kernel); null:
   int step;                    //   this call's 1-based step from the host instead
   const float* gmul;           // device gradient multiplier (clip coefficient): gscale *= gmul[0], once per thread; null: none
-};
+  long long eoff;              // EMA arena's offset from the masters, in floats (EMA instantiations and OPT_SWAP)
+  double ema_decay;            // double: 1 - float(0.9999) is 3e-4 off 1 - 0.9999 relatively
+  int ema_warmup;              // 1: d_n = min(decay, (1 + n) / (10 + n))
+  const int* ema_t;            // EMA updates applied so far, on the device (advanced by opt_tick_kernel); null (stand-alone
+};                             //   kernel only): step - 1
 
 // ---- Adam (torch.optim.Adam / AdamW, no amsgrad, no maximize), fp32 per element:
 //   g' = gscale*g (+ wd*p coupled);  p *= 1 - lr*wd (decoupled);  m += (1-b1)(g' - m);  v = b2*v + (1-b2) g'^2;
@@ -471,6 +477,24 @@ __device__ __forceinline__ void adam1(const AdamCoef& c, float& p, float& m, flo
   p = fmaf(-c.step_size, m / denom, p);
 }
 
+// ---- EMA of the parameters: e += w * (p - e), w = float(1 - d_n), d_n = min(decay, (1 + n) / (10 + n)) with warm-up,
+// decay without; n = updates applied so far.  d_n and 1 - d_n are formed in double once per thread (as adam_coef), the
+// update is one fp32 subtraction and one fma.  One pair of functions for the fused and the stand-alone kernel.
+__device__ __forceinline__ float ema_coef(const OptArgs& a) {
+  const int n = (a.ema_t != nullptr) ? a.ema_t[0] : a.step - 1;
+  double d = a.ema_decay;
+  if (a.ema_warmup) d = fmin(d, (1.0 + (double)n) / (10.0 + (double)n));
+  return (float)(1.0 - d);
+}
+__device__ __forceinline__ float ema1(float w, float p, float e) {
+#pragma clang fp contract(off)
+  const float diff = p - e;
+  return fmaf(w, diff, e);
+}
+__device__ __forceinline__ float4 ema4(float w, float4 p, float4 e) {
+  return make_float4(ema1(w, p.x, e.x), ema1(w, p.y, e.y), ema1(w, p.z, e.z), ema1(w, p.w, e.w));
+}
+
 // The new optimizers' packs are the 16-bit rounding of the fp32 master as stored: without the barrier the compiler
 // folds the update's last fma into the conversion (v_fma_mixlo_f16: the exact fma result rounded once, to fp16), which
 // differs from a re-pack of the stored master in rare double-rounding cases.  (OPT_NONE / OPT_SGD: code unchanged.)
@@ -480,8 +504,11 @@ __device__ __forceinline__ float as_stored(float x) {
   return x;
 }
 
-template <int DT, int OPT>
+// EMA (optimizer instantiations only): every path that stores an updated master also updates its EMA copy at
+// pw[eoff] from the master as stored -- one more fp32 read and write per element, no re-read of the masters.
+template <int DT, int OPT, bool EMA = false>
 __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __restrict__ desc, OptArgs sa) {
+  static_assert(!EMA || (OPT >= OPT_SGD && OPT <= OPT_ADAM), "EMA rides on an optimizer step");
   __shared__ unsigned short t[32][32 * 9 + 2];       // [co][ci*taps + tap] bf16 bits
   const long long* d = desc + (size_t)blockIdx.y * kPackRow;
   float* w = reinterpret_cast<float*>(d[0]);
@@ -490,7 +517,7 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
   const int Co = (int)d[3], Ci = (int)d[4], taps = (int)d[5], first = (int)d[6];
   const int mode = (int)d[7];
   float lr = sa.lr;
-  if constexpr (OPT != OPT_NONE) {
+  if constexpr (OPT != OPT_NONE && OPT != OPT_SWAP) {
     if (sa.flags != nullptr) {
       const bool bad_loss = sa.flags[0] != 0.f;
       if (bad_loss && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) sa.flags[3] = 1.f;
@@ -502,15 +529,19 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
     }
   }
   AdamCoef ac{};                // Adam: filled in below, past the exits of the blocks that have no work
+  float ew = 0.f;               // EMA: likewise
   // one element of the SGD step (sgd_momentum_kernel's order of operations)
   // (explicit multiply / fma: the same rounding steps in both kernels whatever the compiler would contract)
   auto step1 = [&](float* pw, float pv, float gv, float bv) -> float {
+    float ev = 0.f;
+    if constexpr (EMA) ev = pw[sa.eoff];
     if constexpr (OPT == OPT_ADAM) {
       float vv = pw[sa.voff];
       adam1(ac, pv, bv, vv, gv);
       pw[sa.boff] = bv;
       pw[sa.voff] = vv;
       pw[0] = pv;
+      if constexpr (EMA) pw[sa.eoff] = ema1(ew, as_stored<OPT>(pv), ev);
       return pv;
     } else {
       gv = __fmul_rn(gv, sa.gscale);
@@ -519,34 +550,48 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
       pw[sa.boff] = b;
       const float np = fmaf(-lr, b, pv);
       pw[0] = np;
+      if constexpr (EMA) pw[sa.eoff] = ema1(ew, as_stored<OPT>(np), ev);
       return np;
     }
+  };
+  // one element of the swap: the EMA copy lands in the master slot (and is what the packs are made from)
+  auto swap1 = [&](float* pw) -> float {
+    const float pv = pw[0], ev = pw[sa.eoff];
+    pw[sa.eoff] = pv;
+    pw[0] = ev;
+    return ev;
   };
   if (mode < 0) {
     if constexpr (OPT != OPT_NONE) {
       const long long n = d[11];
-      if constexpr (OPT == OPT_ADAM) {
+      if constexpr (OPT == OPT_ADAM || EMA) {
         if ((long long)blockIdx.x * 4096 >= n) return;
-        ac = adam_coef(sa, lr);
+        if constexpr (OPT == OPT_ADAM) ac = adam_coef(sa, lr);
+        if constexpr (EMA) ew = ema_coef(sa);
       }
       const long long e1 = min(n, (long long)(blockIdx.x + 1) * 4096);
-      for (long long i = (long long)blockIdx.x * 4096 + threadIdx.x; i < e1; i += 256)
-        step1(w + i, w[i], w[i + sa.goff], w[i + sa.boff]);
+      for (long long i = (long long)blockIdx.x * 4096 + threadIdx.x; i < e1; i += 256) {
+        if constexpr (OPT == OPT_SWAP) swap1(w + i);
+        else step1(w + i, w[i], w[i + sa.goff], w[i + sa.boff]);
+      }
     }
     return;
   }
   const int nci = (Ci + 31) / 32, nco = (Co + 31) / 32;
   if ((int)blockIdx.x >= nci * nco) return;
   if constexpr (OPT == OPT_ADAM) ac = adam_coef(sa, lr);
+  if constexpr (EMA) ew = ema_coef(sa);
   const int co0 = (blockIdx.x / nci) * 32, ci0 = (blockIdx.x % nci) * 32;
   const int cis = min(32, Ci - ci0), cos_ = min(32, Co - co0);
   const int row = cis * taps;                          // contiguous floats per co in the tile
   // whole 32 x 32 tiles of 8-aligned channel counts (every non-first layer): 16-B loads and stores, 8 channels
   // per thread (the 2-byte-store form took 81 us per step for the 41 M weights); ragged tiles: element-wise
-  const bool v4 = !first && cis == 32 && cos_ == 32 && Ci % 8 == 0 && Co % 8 == 0 && (row & 3) == 0 &&
-                  ((((size_t)co0 * Ci + ci0) * taps) & 3) == 0 && (((size_t)Ci * taps) & 3) == 0 &&
-                  ((uintptr_t)w & 15) == 0 &&
-                  (OPT == OPT_NONE || ((sa.goff | sa.boff | sa.voff) & 3) == 0);   // every arena 16-B aligned
+  // (v4n: the guard of the step without EMA)
+  const bool v4n = !first && cis == 32 && cos_ == 32 && Ci % 8 == 0 && Co % 8 == 0 && (row & 3) == 0 &&
+                   ((((size_t)co0 * Ci + ci0) * taps) & 3) == 0 && (((size_t)Ci * taps) & 3) == 0 &&
+                   ((uintptr_t)w & 15) == 0 &&
+                   (OPT == OPT_NONE || ((sa.goff | sa.boff | sa.voff) & 3) == 0);   // every arena 16-B aligned
+  const bool v4 = v4n && (!(EMA || OPT == OPT_SWAP) || (sa.eoff & 3) == 0);
   if (v4 && OPT == OPT_ADAM) {
     // Adam: the next iteration's four loads are issued ahead of this one's arithmetic and stores.  The iterations
     // touch distinct addresses, which the compiler cannot prove (the stores through pw + boff / voff may alias the
@@ -559,25 +604,27 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
     };
     int i = threadIdx.x, c = 0, r = 0;
     float* pw = w;
-    float4 v{}, gv{}, m{}, s{};
+    float4 v{}, gv{}, m{}, s{}, e{};
     if (i < total) {
       pw = at(i, c, r);
       v = *reinterpret_cast<const float4*>(pw);
       gv = *reinterpret_cast<const float4*>(pw + sa.goff);
       m = *reinterpret_cast<const float4*>(pw + sa.boff);
       s = *reinterpret_cast<const float4*>(pw + sa.voff);
+      if constexpr (EMA) e = *reinterpret_cast<const float4*>(pw + sa.eoff);
     }
     while (i < total) {
       const int in = i + 256;
       int cn = 0, rn = 0;
       float* pwn = pw;
-      float4 vn{}, gvn{}, mn{}, sn{};
+      float4 vn{}, gvn{}, mn{}, sn{}, en{};
       if (in < total) {
         pwn = at(in, cn, rn);
         vn = *reinterpret_cast<const float4*>(pwn);
         gvn = *reinterpret_cast<const float4*>(pwn + sa.goff);
         mn = *reinterpret_cast<const float4*>(pwn + sa.boff);
         sn = *reinterpret_cast<const float4*>(pwn + sa.voff);
+        if constexpr (EMA) en = *reinterpret_cast<const float4*>(pwn + sa.eoff);
       }
       adam1(ac, v.x, m.x, s.x, gv.x); adam1(ac, v.y, m.y, s.y, gv.y);
       adam1(ac, v.z, m.z, s.z, gv.z); adam1(ac, v.w, m.w, s.w, gv.w);
@@ -585,8 +632,10 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
       *reinterpret_cast<float4*>(pw + sa.voff) = s;
       *reinterpret_cast<float4*>(pw) = v;
       v.x = as_stored<OPT>(v.x); v.y = as_stored<OPT>(v.y); v.z = as_stored<OPT>(v.z); v.w = as_stored<OPT>(v.w);
+      if constexpr (EMA) *reinterpret_cast<float4*>(pw + sa.eoff) = ema4(ew, v, e);
       t[c][r] = f2h<DT>(v.x); t[c][r + 1] = f2h<DT>(v.y); t[c][r + 2] = f2h<DT>(v.z); t[c][r + 3] = f2h<DT>(v.w);
       i = in; pw = pwn; c = cn; r = rn; v = vn; gv = gvn; m = mn; s = sn;
+      if constexpr (EMA) e = en;
     }
   } else if (v4) {
     const int r4 = row >> 2;
@@ -594,9 +643,16 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
       const int c = i / r4, r = (i - c * r4) * 4;
       float* pw = w + ((size_t)(co0 + c) * Ci + ci0) * taps + r;
       float4 v = *reinterpret_cast<const float4*>(pw);
-      if constexpr (OPT != OPT_NONE && OPT != OPT_ADAM) {
+      if constexpr (OPT == OPT_SWAP) {
+        const float4 e = *reinterpret_cast<const float4*>(pw + sa.eoff);
+        *reinterpret_cast<float4*>(pw + sa.eoff) = v;
+        *reinterpret_cast<float4*>(pw) = e;
+        v = e;
+      } else if constexpr (OPT != OPT_NONE && OPT != OPT_ADAM) {
         float4 gv = *reinterpret_cast<const float4*>(pw + sa.goff);
         float4 b = *reinterpret_cast<const float4*>(pw + sa.boff);
+        float4 e{};
+        if constexpr (EMA) e = *reinterpret_cast<const float4*>(pw + sa.eoff);
         gv.x = __fmul_rn(gv.x, sa.gscale); gv.y = __fmul_rn(gv.y, sa.gscale);
         gv.z = __fmul_rn(gv.z, sa.gscale); gv.w = __fmul_rn(gv.w, sa.gscale);
         if constexpr (OPT == OPT_SGD_WD) {
@@ -608,18 +664,38 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
         *reinterpret_cast<float4*>(pw + sa.boff) = b;
         v.x = fmaf(-lr, b.x, v.x); v.y = fmaf(-lr, b.y, v.y); v.z = fmaf(-lr, b.z, v.z); v.w = fmaf(-lr, b.w, v.w);
         *reinterpret_cast<float4*>(pw) = v;
+        if constexpr (EMA)
+          *reinterpret_cast<float4*>(pw + sa.eoff) =
+              ema4(ew, make_float4(as_stored<OPT>(v.x), as_stored<OPT>(v.y), as_stored<OPT>(v.z), as_stored<OPT>(v.w)), e);
       }
       v.x = as_stored<OPT>(v.x); v.y = as_stored<OPT>(v.y); v.z = as_stored<OPT>(v.z); v.w = as_stored<OPT>(v.w);
       t[c][r] = f2h<DT>(v.x); t[c][r + 1] = f2h<DT>(v.y); t[c][r + 2] = f2h<DT>(v.z); t[c][r + 3] = f2h<DT>(v.w);
     }
   } else {
-    for (int i = threadIdx.x; i < cos_ * row; i += 256) {
-      const int c = i / row, r = i - c * row;
-      float* pw = w + ((size_t)(co0 + c) * Ci + ci0) * taps + r;
-      float v = pw[0];
-      if constexpr (OPT != OPT_NONE) v = step1(pw, v, pw[sa.goff], pw[sa.boff]);
-      t[c][r] = f2h<DT>(as_stored<OPT>(v));
+    // OPT_SGD packs a ragged tile from the update's fma folded into the 16-bit conversion (see as_stored) and a v4
+    // tile from the master as stored.  With EMA a whole tile can land here only because the EMA arena is off float4
+    // alignment: it still packs from the master as stored (STORED), so the packs do not depend on where the EMA
+    // arena lies.
+#define CAN_RAGGED_TILE(STORED)                                                             \
+    for (int i = threadIdx.x; i < cos_ * row; i += 256) {                                   \
+      const int c = i / row, r = i - c * row;                                               \
+      float* pw = w + ((size_t)(co0 + c) * Ci + ci0) * taps + r;                            \
+      float v = pw[0];                                                                      \
+      if constexpr (OPT == OPT_SWAP) v = swap1(pw);                                         \
+      else if constexpr (OPT != OPT_NONE) v = step1(pw, v, pw[sa.goff], pw[sa.boff]);       \
+      if constexpr (STORED) asm volatile("" : "+v"(v));                                     \
+      t[c][r] = f2h<DT>(as_stored<OPT>(v));                                                 \
     }
+    if constexpr (EMA && OPT == OPT_SGD) {
+      if (v4n) {
+        CAN_RAGGED_TILE(true)
+      } else {
+        CAN_RAGGED_TILE(false)
+      }
+    } else {
+      CAN_RAGGED_TILE(false)
+    }
+#undef CAN_RAGGED_TILE
   }
   __syncthreads();
   if (first) {
@@ -730,10 +806,31 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float*
 // The device step count t advances by one per APPLIED Adam step: a one-thread launch right after the step kernel,
 // which skips on the same flags.  Every block of the step kernel read t before this launch starts (stream order), so
 // all of them saw the same value; a captured step replays both nodes and its bias correction advances.
-__global__ void opt_tick_kernel(const float* __restrict__ flags, int* __restrict__ t) {
+// t2 (optional): a second count advanced under the same flags -- the EMA's update count beside Adam's step count.
+__global__ void opt_tick_kernel(const float* __restrict__ flags, int* __restrict__ t, int* __restrict__ t2) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   if (flags != nullptr && (flags[0] != 0.f || flags[2] != 0.f)) return;
-  t[0] += 1;
+  if (t != nullptr) t[0] += 1;
+  if (t2 != nullptr) t2[0] += 1;
+}
+
+// ---------------------------------------------------------------- EMA (stand-alone)
+// e += w * (p - e) over flat buffers, per element exactly the fused kernel's ema_coef / ema1 (so "fused == optimizer
+// without EMA, then ema" holds bit for bit); flags as adam_kernel.  vec: both pointers 16-B aligned -> float4 groups,
+// the n % 4 tail (or, unaligned, everything) element-wise.
+__global__ void __launch_bounds__(256) ema_kernel(float* __restrict__ e, const float* __restrict__ p, size_t n, int vec,
+                                                  OptArgs a) {
+  if (a.flags != nullptr) {
+    const bool bad_loss = a.flags[0] != 0.f;
+    if (bad_loss && blockIdx.x == 0 && threadIdx.x == 0) a.flags[3] = 1.f;
+    if (bad_loss || a.flags[2] != 0.f) return;
+  }
+  const float w = ema_coef(a);
+  const size_t n4 = vec ? n / 4 : 0;
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
+    reinterpret_cast<float4*>(e)[i] = ema4(w, reinterpret_cast<const float4*>(p)[i], reinterpret_cast<float4*>(e)[i]);
+  for (size_t i = 4 * n4 + blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    e[i] = ema1(w, p[i], e[i]);
 }
 
 // ---------------------------------------------------------------- gradient norm (global-norm clipping)
@@ -997,37 +1094,105 @@ extern "C" int can_adam(float* p, float* m, float* v, const float* g, size_t n, 
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(vec ? (n + 3) / 4 : n, 256, 4096)), dim3(256), 0, s, p, m, v, g, n, vec,
                      a);
-  if (t_dev != nullptr) hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t_dev);
+  if (t_dev != nullptr)
+    hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t_dev, (int*)nullptr);
+  return (int)hipGetLastError();
+}
+
+// Stand-alone EMA update over flat fp32 buffers (any n, any alignment).  t_dev: the device count of applied updates
+// (advanced by one here unless the update is skipped through flags); null: `step` is this call's 1-based update.
+extern "C" int can_ema(float* e, const float* p, size_t n, double decay, int warmup, int step, int* t_dev, float* flags,
+                       void* stream) {
+  if (!(decay >= 0.0 && decay < 1.0)) return -2;
+  if (t_dev == nullptr && step < 1) return -2;
+  if (n == 0) return 0;
+  OptArgs a{};
+  a.ema_decay = decay; a.ema_warmup = warmup ? 1 : 0; a.ema_t = t_dev; a.step = step; a.flags = flags;
+  const int vec = (((uintptr_t)e | (uintptr_t)p) & 15) == 0;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(vec ? (n + 3) / 4 : n, 256, 4096)), dim3(256), 0, s, e, p, n, vec, a);
+  if (t_dev != nullptr)
+    hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t_dev, (int*)nullptr);
   return (int)hipGetLastError();
 }
 
 // The fused optimizer step for every optimizer: opt 1 = SGD-momentum (can_sgd_pack's kernel), 2 = SGD with coupled
 // weight decay, 3 = Adam / AdamW (mom = first moment, second moment at voff; t_dev required, advanced when applied).
-extern "C" int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
-                            long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
-                            int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt,
-                            void* stream, const float* gmul) {
+static int opt_pack_launch(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
+                           long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
+                           int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt,
+                           void* stream, const float* gmul, bool ema, long long eoff, double ema_decay, int ema_warmup,
+                           int* ema_t) {
   if (rows <= 0) return 0;
   if (opt < OPT_SGD || opt > OPT_ADAM || (opt == OPT_ADAM && t_dev == nullptr)) return -2;
+  if (ema && (ema_t == nullptr || eoff == 0 || !(ema_decay >= 0.0 && ema_decay < 1.0))) return -2;
   if (dt != DT_F16 && dt != DT_BF16) return -20;
   OptArgs sa{};
   sa.goff = goff; sa.boff = boff; sa.voff = (opt == OPT_ADAM) ? voff : 0;
   sa.lr = lr; sa.momentum = momentum; sa.gscale = gscale; sa.wd = wd; sa.eps = eps; sa.decoupled = decoupled;
   sa.beta1 = beta1; sa.beta2 = beta2; sa.flags = flags; sa.lr_dev = lr_dev; sa.t = t_dev; sa.gmul = gmul;
+  if (ema) {
+    sa.eoff = eoff; sa.ema_decay = ema_decay; sa.ema_warmup = ema_warmup ? 1 : 0; sa.ema_t = ema_t;
+  }
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(max_tiles, rows), blk(256);
-#define CAN_OPT_LAUNCH(O)                                                                                       \
+#define CAN_OPT_LAUNCH(O, E)                                                                                    \
   do {                                                                                                           \
-    if (dt == DT_F16) hipLaunchKernelGGL((pack_multi_kernel<DT_F16, O>), grid, blk, 0, s, desc, sa);             \
-    else hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, O>), grid, blk, 0, s, desc, sa);                          \
+    if (dt == DT_F16) hipLaunchKernelGGL((pack_multi_kernel<DT_F16, O, E>), grid, blk, 0, s, desc, sa);          \
+    else hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, O, E>), grid, blk, 0, s, desc, sa);                       \
   } while (0)
-  if (opt == OPT_SGD) CAN_OPT_LAUNCH(OPT_SGD);
-  else if (opt == OPT_SGD_WD) CAN_OPT_LAUNCH(OPT_SGD_WD);
-  else {
-    CAN_OPT_LAUNCH(OPT_ADAM);
-    hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t_dev);
+  if (!ema) {
+    if (opt == OPT_SGD) CAN_OPT_LAUNCH(OPT_SGD, false);
+    else if (opt == OPT_SGD_WD) CAN_OPT_LAUNCH(OPT_SGD_WD, false);
+    else CAN_OPT_LAUNCH(OPT_ADAM, false);
+  } else {
+    if (opt == OPT_SGD) CAN_OPT_LAUNCH(OPT_SGD, true);
+    else if (opt == OPT_SGD_WD) CAN_OPT_LAUNCH(OPT_SGD_WD, true);
+    else CAN_OPT_LAUNCH(OPT_ADAM, true);
   }
 #undef CAN_OPT_LAUNCH
+  // the counts advance in one one-thread launch right after the step, under the step's flags
+  int* t1 = (opt == OPT_ADAM) ? t_dev : nullptr;
+  int* t2 = ema ? ema_t : nullptr;
+  if (t1 != nullptr || t2 != nullptr)
+    hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t1, t2);
+  return (int)hipGetLastError();
+}
+
+extern "C" int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
+                            long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
+                            int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt,
+                            void* stream, const float* gmul) {
+  return opt_pack_launch(desc, rows, max_tiles, opt, goff, boff, voff, lr, momentum, beta1, beta2, eps, wd, decoupled,
+                         gscale, t_dev, flags, lr_dev, dt, stream, gmul, false, 0, 0.0, 0, nullptr);
+}
+
+// can_opt_pack with the EMA of the parameters updated in the same launch: the EMA arena eoff floats from the masters,
+// ema_t the device count of applied updates (required; advanced with the step, for every optimizer).  Refuses a decay
+// outside [0, 1).
+extern "C" int can_opt_pack_ema(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
+                                long long voff, float lr, float momentum, double beta1, double beta2, float eps,
+                                float wd, int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev,
+                                int dt, void* stream, const float* gmul, long long eoff, double ema_decay,
+                                int ema_warmup, int* ema_t) {
+  return opt_pack_launch(desc, rows, max_tiles, opt, goff, boff, voff, lr, momentum, beta1, beta2, eps, wd, decoupled,
+                         gscale, t_dev, flags, lr_dev, dt, stream, gmul, true, eoff, ema_decay, ema_warmup, ema_t);
+}
+
+// The swap launch (pack_multi_kernel<DT, OPT_SWAP>): every master exchanged with its EMA copy eoff floats away, over
+// the optimizer's descriptor rows, and every pack written from what lands in the master slot.  No flags: it always runs.
+extern "C" int can_swap_pack(const long long* desc, int rows, int max_tiles, long long eoff, int dt, void* stream) {
+  if (rows <= 0) return 0;
+  if (eoff == 0) return -2;
+  OptArgs sa{};
+  sa.eoff = eoff;
+  hipStream_t s = (hipStream_t)stream;
+  if (dt == DT_F16)
+    hipLaunchKernelGGL((pack_multi_kernel<DT_F16, OPT_SWAP>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
+  else if (dt == DT_BF16)
+    hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, OPT_SWAP>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
+  else
+    return -20;
   return (int)hipGetLastError();
 }
 

@@ -49,6 +49,11 @@ re-designed for MI355X:
   update; ``clip_grad_norm=m`` adds a two-launch fixed-order norm pass over the accumulated, all-reduced arena whose
   clip coefficient the optimizer kernel reads from the device (``_step_tail``, README "Gradient accumulation and
   clipping").  With the defaults the step issues exactly the launches it issued before.
+* ``ema_decay=d`` (0 = off) keeps an fp32 exponential moving average of every parameter in a fourth arena
+  (``self.ema``), updated by the fused optimizer launch itself from the masters it holds in registers (one more read and
+  write of the arena, no extra pass; a one-thread tick advances the device count ``ema_t`` that the warm-up
+  d_n = min(d, (1 + n) / (10 + n)) reads, so a captured step needs nothing new).  ``ema_weights()`` swaps the
+  average into the model for evaluation and checkpointing and swaps the raw weights back (README "EMA weights").
 
 CU budget of the gradient all-reduce (``comm_ctas``, default 8 = parallel.reducer.DEFAULT_COMM_CTAS): the owned RCCL
 communicator is created with ncclConfig_t.minCTAs = maxCTAs = comm_ctas, so its kernels occupy exactly that many of
@@ -78,6 +83,7 @@ from ..ops import _ext
 from ..ops.executor import CANNetExecutor
 from ..utils.flat import FlatArena
 from ..utils.profiling import trace_range
+from .trainer import check_ema_decay
 
 ACT_DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
@@ -164,7 +170,8 @@ class NativeStepper:
                  reducer_transport: Optional[str] = None, init_scale="auto", scale_interval: int = 2000,
                  graph_max_shapes: int = 8, comm_ctas: Optional[int] = None, graph_bind_inputs: bool = False,
                  optimizer: str = "sgd", weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 accum_steps: int = 1, clip_grad_norm: float = 0.0):
+                 accum_steps: int = 1, clip_grad_norm: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True):
+        check_ema_decay(ema_decay)
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         if int(accum_steps) != accum_steps or accum_steps < 1:
@@ -198,7 +205,14 @@ class NativeStepper:
         self.mom2 = torch.zeros_like(self.arena.data) if optimizer != "sgd" else None
         self.opt_t = torch.zeros(1, dtype=torch.int32, device=self.device) if optimizer != "sgd" else None
         self.grads = self.arena.grad_views()
-        self.ex.opt_prepare(self.arena.data, self.arena.grad, self.mom, self.mom2)   # (device descriptor: before any capture)
+        # EMA of the parameters (0 = off: no arena, and the default step keeps sgd_step): filled from the masters at
+        # the end of the constructor, once the weights are final (after the rank-0 broadcast)
+        self.ema_decay = float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = torch.zeros_like(self.arena.data) if self.ema_decay > 0 else None
+        self.ema_t = torch.zeros(1, dtype=torch.int32, device=self.device) if self.ema is not None else None
+        self._ema_in = False                         # inside ema_weights(): the arena holds the average
+        self.ex.opt_prepare(self.arena.data, self.arena.grad, self.mom, self.mom2, self.ema)   # (device descriptor: before any capture)
         # [non-finite loss (any rank after the all-reduce), loss, non-finite gradient (fp16), sticky non-finite]
         self.flags = torch.zeros(4, dtype=torch.float32, device=self.device)
         # gradient accumulation: a window of accum_steps micro-steps is ONE optimizer step on the sum of their
@@ -245,6 +259,8 @@ class NativeStepper:
         self.reducer_transport = None if self.reducer is None else self.reducer.transport
         if world > 1:
             self._broadcast_params()
+        if self.ema is not None:
+            self.ema.copy_(self.arena.data)
         if graph not in (True, False, "auto"):
             raise ValueError(f"graph must be True, False or 'auto', got {graph!r}")
         self.use_graph = graph
@@ -360,14 +376,16 @@ class NativeStepper:
             return self.flags[1:2]
         with trace_range("cannet/sgd"):
             # the optimizer over the arena and the 16-bit weight packs in ONE launch (executor.sgd_step / opt_step)
-            if self.optimizer == "sgd" and self.weight_decay == 0 and not clip:
+            if self.optimizer == "sgd" and self.weight_decay == 0 and not clip and self.ema is None:
                 ex.sgd_step(self.arena.data, self.arena.grad, self.mom, self._lr, self.momentum, 1.0 / self.world,
                             flags=self.flags, lr_dev=self._lr_dev)
             else:
                 ex.opt_step(self.arena.data, self.arena.grad, self.mom, self._lr, 1.0 / self.world,
                             optimizer=self.optimizer, momentum=self.momentum, weight_decay=self.weight_decay,
                             betas=self.betas, eps=self.eps, mom2=self.mom2, step=self.opt_t, flags=self.flags,
-                            lr_dev=self._lr_dev, gmul=self.gn[1:2] if clip else None)
+                            lr_dev=self._lr_dev, gmul=self.gn[1:2] if clip else None,
+                            **(dict(ema=self.ema, ema_t=self.ema_t, ema_decay=self.ema_decay,
+                                    ema_warmup=self.ema_warmup) if self.ema is not None else {}))
             if sc is not None:
                 self.C.scale_update(self.flags.data_ptr() + 8, sc.data_ptr(), int(self.scale_interval), 2.0, 0.5,
                                     float(2 ** 24), st)
@@ -427,6 +445,8 @@ class NativeStepper:
         """One micro-step.  Returns the loss (summed over ranks; with accum_steps > 1: over the window's micro-batches
         too) as a device scalar on the call that closes a window, None on the others.  ``skipped_last()``, the sticky
         non-finite flag, Adam's step count and the fp16 loss scale all advance per window."""
+        if self._ema_in:
+            raise RuntimeError("step() inside ema_weights(): the model holds the averaged weights")
         if img.device != self.device:
             img = img.to(self.device, non_blocking=True)
         if gt.device != self.device:
@@ -490,6 +510,52 @@ class NativeStepper:
         self._micro = 0
         self._loss = out
         return out
+
+    # ------------------------------------------------------------ EMA
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model holds the EMA weights: one swap launch exchanges the master arena with the EMA
+        arena and re-packs (the parameters are views of the arena, so ``model(img)``, ``state_dict()`` and
+        ``save_checkpoint`` see the average; no address changes, captured graphs stay valid); the exit swaps back, bit
+        for bit.  Raises inside an open accumulation window (call ``flush()`` first) and when EMA is off."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights(): EMA is off (ema_decay = 0)")
+        if self._micro != 0:
+            raise RuntimeError("ema_weights(): an accumulation window is open; call flush() first")
+        if self._ema_in:
+            raise RuntimeError("ema_weights() does not nest")
+        self.ex.swap_weights(self.arena.data, self.ema)
+        self._ema_in = True
+        try:
+            yield self.model
+        finally:
+            self.ex.swap_weights(self.arena.data, self.ema)
+            self._ema_in = False
+
+    def ema_state(self) -> Optional[dict]:
+        """{"ema": {parameter name: averaged tensor (a clone)}, "steps": updates applied}, keyed like ``state_dict``;
+        None when EMA is off."""
+        if self.ema is None:
+            return None
+        src = self.arena.data if self._ema_in else self.ema
+        out = {}
+        for (name, _), (off, n), p in zip(self.model.named_parameters(), self.arena.offsets, self.params):
+            out[name] = src[off:off + n].view_as(p).clone()
+        return {"ema": out, "steps": int(self.ema_t.item())}
+
+    def load_ema_state(self, ema: Optional[dict], steps: int = 0) -> bool:
+        """Restore the average from a name-keyed dict (either stepper family's ``ema_state()["ema"]``); None: restart
+        it from the current weights at n = 0.  Returns whether a saved average was loaded."""
+        if self.ema is None:
+            return False
+        if not ema:
+            self.ema.copy_(self.arena.data)
+            self.ema_t.zero_()
+            return False
+        for (name, _), (off, n) in zip(self.model.named_parameters(), self.arena.offsets):
+            self.ema[off:off + n].copy_(ema[name].reshape(-1).to(self.device))
+        self.ema_t.fill_(int(steps))
+        return True
 
     def grad_norm(self) -> Optional[float]:
         """Global 2-norm of the last window's accumulated, averaged gradient, before clipping (None: clipping off).
@@ -618,6 +684,8 @@ class NativeStepper:
             st["opt_steps"] = int(self.opt_t.item())
         if self.scaler is not None:
             st["scaler"] = self.scaler
+        if self.ema is not None:
+            st.update(ema_steps=int(self.ema_t.item()), ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
         return st
 
     def load_resume_state(self, st: Optional[dict]):
@@ -633,6 +701,8 @@ class NativeStepper:
         self.steps = int(st.get("steps", self.steps))
         if self.scaler is not None and st.get("scaler") is not None:
             self.scaler.copy_(st["scaler"].to(self.scaler.device))
+        if self.ema is not None and st.get("ema_steps") is not None:
+            self.ema_t.fill_(int(st["ema_steps"]))
         self.ex.refresh_packs(force=True)
 
     def last_loss(self) -> Optional[float]:

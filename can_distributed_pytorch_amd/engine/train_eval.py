@@ -40,14 +40,15 @@ def _progress(it, enabled):
 
 
 def train_one_epoch(model, optimizer, train_loader, device, epoch, log=None, accum_steps: int = 1,
-                    clip_grad_norm: float = 0.0):
+                    clip_grad_norm: float = 0.0, on_step=None):
     """Generic autograd path (any model/optimizer, DDP or our hook reducer).
 
     accum_steps > 1: one optimizer step per window of accum_steps batches on the sum of their gradients (the loss is
     sum-reduced: no 1/k, lr not rescaled) -- zero_grad at a window's start, DDP ``no_sync()`` on its non-closing
     batches, and a window still open at the end of the epoch is closed there (for DDP the loader's last batch always
     runs synchronised, so that flush has the all-reduced gradient).  clip_grad_norm > 0:
-    torch.nn.utils.clip_grad_norm_ ahead of every optimizer step."""
+    torch.nn.utils.clip_grad_norm_ ahead of every optimizer step.  on_step: called after every optimizer step (the
+    EMA update of the stepper that owns the optimizer)."""
     model.train()
     criterion = torch.nn.MSELoss(reduction="sum")
     mean_loss = torch.zeros(1, device=device)
@@ -63,6 +64,8 @@ def train_one_epoch(model, optimizer, train_loader, device, epoch, log=None, acc
         if clip_grad_norm > 0:
             torch.nn.utils.clip_grad_norm_([p for p in params if p.grad is not None], clip_grad_norm)
         optimizer.step()
+        if on_step is not None:
+            on_step()
 
     for step, (img, gt) in enumerate(loader):
         if micro == 0:

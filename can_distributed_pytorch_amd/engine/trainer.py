@@ -34,6 +34,100 @@ def _check_window(accum_steps, clip_grad_norm):
         raise ValueError(f"clip_grad_norm must be >= 0 (0 = off, inf = measure only), got {clip_grad_norm!r}")
 
 
+def check_ema_decay(d):
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1) (0 = off), got {d!r}")
+
+
+def ema_decay_at(n: int, decay: float, warmup: bool = True) -> float:
+    """d_n of the n-th (0-based) EMA update, in Python doubles: min(decay, (1 + n) / (10 + n)) with warm-up."""
+    return min(decay, (1.0 + n) / (10.0 + n)) if warmup else decay
+
+
+class ParamEma:
+    """EMA of the parameters for the steppers whose optimizer runs in torch ops: per-parameter fp32 copies, updated
+    after every applied optimizer step by e += w (p - e), w = float32(1 - d_n) (engine/native.py has the semantics and
+    the fused kernel), and exchanged with the parameters' ``.data`` by ``ema_weights()``.  BatchNorm buffers are not
+    averaged.  No communication: the average is a deterministic function of replicated weights."""
+
+    def _ema_init(self, ema_decay: float, ema_warmup: bool):
+        check_ema_decay(ema_decay)
+        self.ema_decay = float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_steps = 0
+        self._ema = None
+        self._ema_in = False
+
+    def _ema_params(self):
+        return list(self.model.parameters())
+
+    def ema_start(self):
+        """(Re)start the average from the current weights at n = 0 (call once the weights are final)."""
+        if self.ema_decay > 0:
+            self._ema = [p.detach().clone().float() for p in self._ema_params()]
+            self.ema_steps = 0
+
+    def ema_update(self):
+        """One EMA update (after an applied optimizer step)."""
+        if self._ema is None:
+            return
+        d = ema_decay_at(self.ema_steps, self.ema_decay, self.ema_warmup)
+        w = float(torch.tensor(1.0 - d, dtype=torch.float64).float())
+        with torch.no_grad():
+            for e, p in zip(self._ema, self._ema_params()):
+                e.add_(p.detach().float() - e, alpha=w)
+        self.ema_steps += 1
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model holds the EMA weights (``.data`` exchanged); the exit restores the raw weights,
+        bit for bit.  Raises inside an open accumulation window and when EMA is off."""
+        if self._ema is None:
+            raise RuntimeError("ema_weights(): EMA is off (ema_decay = 0)")
+        if self._micro != 0:
+            raise RuntimeError("ema_weights(): an accumulation window is open; call flush() first")
+        if self._ema_in:
+            raise RuntimeError("ema_weights() does not nest")
+        ps = self._ema_params()
+
+        def swap():
+            for i, p in enumerate(ps):
+                raw = p.data
+                p.data = self._ema[i].to(raw.dtype)
+                self._ema[i] = raw
+        swap()
+        self._ema_in = True
+        try:
+            yield self.model
+        finally:
+            # back: the raw tensors return to the parameters untouched; the average was not changed inside
+            for i, p in enumerate(ps):
+                raw, avg = self._ema[i], p.data
+                p.data = raw
+                self._ema[i] = avg.float()
+            self._ema_in = False
+
+    def ema_state(self) -> Optional[dict]:
+        if self._ema is None:
+            return None
+        names = [n for n, _ in self.model.named_parameters()]
+        src = [p.data for p in self._ema_params()] if self._ema_in else self._ema
+        return {"ema": {n: e.detach().float().clone() for n, e in zip(names, src)}, "steps": int(self.ema_steps)}
+
+    def load_ema_state(self, ema: Optional[dict], steps: int = 0) -> bool:
+        """Restore the average from a name-keyed dict (any stepper's ``ema_state()["ema"]``); None: restart it from
+        the current weights at n = 0.  Returns whether a saved average was loaded."""
+        if self.ema_decay <= 0:
+            return False
+        if not ema:
+            self.ema_start()
+            return False
+        self._ema = [ema[n].detach().to(p.device).float().clone().view_as(p)
+                     for n, p in self.model.named_parameters()]
+        self.ema_steps = int(steps)
+        return True
+
+
 def make_torch_optimizer(params, optimizer="sgd", lr=1e-7, momentum=0.95, weight_decay=0.0, betas=(0.9, 0.999),
                          eps=1e-8):
     """torch.optim.SGD / Adam / AdamW from the steppers' common optimizer arguments."""
@@ -46,13 +140,14 @@ def make_torch_optimizer(params, optimizer="sgd", lr=1e-7, momentum=0.95, weight
     raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
 
 
-class TorchStepper:
+class TorchStepper(ParamEma):
     exec_backend = "torch"
 
     def __init__(self, device, dtype="fp32", world=1, lr=1e-7, momentum=0.95, channels_last=None, model=None,
                  bucket_mb: float = 25.0, optimizer="sgd", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8,
-                 accum_steps: int = 1, clip_grad_norm: float = 0.0):
+                 accum_steps: int = 1, clip_grad_norm: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True):
         _check_window(accum_steps, clip_grad_norm)
+        self._ema_init(ema_decay, ema_warmup)
         # gradient accumulation / global-norm clipping, the stock way: zero_grad at a window's start, DDP no_sync()
         # on its non-closing micro-steps, torch.nn.utils.clip_grad_norm_ ahead of the optimizer (engine/native.py has
         # the semantics: the sum-reduced loss needs no 1/k, lr is not rescaled)
@@ -81,6 +176,7 @@ class TorchStepper:
         self._loss = None
         self.autocast = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(dtype)
         self.scaler = torch.amp.GradScaler("cuda") if dtype == "fp16" else None
+        self.ema_start()                # (world > 1: DDP's constructor has broadcast rank 0's weights)
 
     def step(self, img, gt):
         """One micro-step; returns the window's loss on the call that closes it (accum_steps = 1: every call), else
@@ -116,10 +212,14 @@ class TorchStepper:
             self._grad_norm = torch.nn.utils.clip_grad_norm_(
                 [p for p in self.model.parameters() if p.grad is not None], self.clip_grad_norm)
         if self.scaler is not None:
+            before = self.scaler.get_scale() if self._ema is not None else None
             self.scaler.step(self.opt)
             self.scaler.update()
+            if before is None or self.scaler.get_scale() >= before:      # (a backed-off scale: the step was skipped)
+                self.ema_update()
         else:
             self.opt.step()
+            self.ema_update()
         self._micro = 0
         self._loss = self._acc
         return self._loss
@@ -151,7 +251,7 @@ class Fp32Stepper(TorchStepper):
         super().__init__(device, dtype="fp32", channels_last=False, **kw)
 
 
-class ArenaStepper:
+class ArenaStepper(ParamEma):
     """This framework's data-parallel engine on the plain-ATen CANNet: the CPU / gloo rehearsal of the native step's
     distributed path (engine/native.py), used by ``bench.py --device cpu`` and the multi-process CPU tests.
 
@@ -164,9 +264,10 @@ class ArenaStepper:
 
     def __init__(self, device="cpu", world=1, lr=1e-7, momentum=0.95, model=None, bucket_mb: float = 25.0,
                  optimizer="sgd", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, accum_steps: int = 1,
-                 clip_grad_norm: float = 0.0):
+                 clip_grad_norm: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True):
         from ..models.cannet import grad_ready_order
         _check_window(accum_steps, clip_grad_norm)
+        self._ema_init(ema_decay, ema_warmup)
         self.accum_steps = int(accum_steps)
         self.clip_grad_norm = float(clip_grad_norm)
         self._micro = 0
@@ -201,6 +302,7 @@ class ArenaStepper:
         self._loss = None
         if world > 1:
             self.reducer.broadcast_arena(0)
+        self.ema_start()
 
     def step(self, img, gt):
         """One micro-step (the native step's window: engine/native.py): the arena is zeroed at a window's start only,
@@ -233,8 +335,8 @@ class ArenaStepper:
             self.flags[0] = 0.0 if bool(torch.isfinite(self._acc)) else 1.0
             self.flags[1] = self._acc
             red.allreduce_scalars(self.flags)
-            if self.flags[0] == 0:
-                self._update()
+            if self.flags[0] == 0 and self._update() is not False:
+                self.ema_update()
         self._micro = 0
         self._loss = self.flags[1:2] / self.world
         return self._loss
@@ -275,7 +377,7 @@ class ArenaStepper:
         p, g, wd = self.arena.data, self.arena.grad, self.weight_decay
         gs = self._clip()
         if gs is None:
-            return
+            return False                                     # skipped (non-finite norm): no EMA update either
         if self.optimizer == "sgd":
             # buf = m * buf + g / W (+ wd * p) ; p -= lr * buf   (torch.optim.SGD semantics, zero-initialised buffer)
             if wd != 0:
@@ -315,9 +417,10 @@ def build_trainer(impl="hip", dtype="bf16", device="cuda", world=1, lr=1e-7, bat
                   reducer_transport: Optional[str] = None, comm_ctas: Optional[int] = None,
                   graph_bind_inputs: bool = False, graph_max_shapes: int = 8, optimizer: str = "sgd",
                   momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                  accum_steps: int = 1, clip_grad_norm: float = 0.0):
+                  accum_steps: int = 1, clip_grad_norm: float = 0.0, ema_decay: float = 0.0,
+                  ema_warmup: bool = True):
     opt = dict(optimizer=optimizer, momentum=momentum, weight_decay=weight_decay, betas=betas, eps=eps,
-               accum_steps=accum_steps, clip_grad_norm=clip_grad_norm)
+               accum_steps=accum_steps, clip_grad_norm=clip_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
     if impl == "arena":
         return ArenaStepper(device, world=world, lr=lr, model=model, bucket_mb=bucket_mb, **opt)
     if impl == "torch":

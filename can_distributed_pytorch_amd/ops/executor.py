@@ -240,15 +240,24 @@ class CANNetExecutor(ContextSchedule):
                  optimizer: str = "sgd", momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999),
                  eps: float = 1e-8, mom2: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None,
                  flags: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None,
-                 gmul: Optional[torch.Tensor] = None):
+                 gmul: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None,
+                 ema_t: Optional[torch.Tensor] = None, ema_decay: float = 0.0, ema_warmup: bool = True):
         """The fused optimizer step for every optimizer (elementwise.hip pack_multi_kernel<DT, OPT>), ONE launch over
         the arena that also writes the 16-bit packs, as ``sgd_step``: ``optimizer`` = "sgd" (torch.optim.SGD with
         momentum and coupled ``weight_decay``; weight decay 0 runs sgd_step's kernel), "adam" (torch.optim.Adam,
         coupled weight decay) or "adamw" (decoupled).  Adam: ``mom`` / ``mom2`` are the first / second moment arenas
         and ``step`` the int32 device count of applied steps, which a one-thread launch after the step advances
         unless the step was skipped through ``flags``.  ``gmul``: an fp32 device scalar the kernel multiplies into
-        ``gscale`` (one fp32 product: the clip coefficient of ``grad_norm``)."""
-        desc, rows, tiles, goff, boff, voff = self.opt_prepare(data, grad, mom, mom2)
+        ``gscale`` (one fp32 product: the clip coefficient of ``grad_norm``).  ``ema``: an fp32 arena like ``data``
+        holding the exponential moving average of the parameters, updated in the same launch from the masters as
+        stored (e += w (p - e), w = 1 - min(ema_decay, (1 + n) / (10 + n)) with ``ema_warmup``, n = ``ema_t``, the
+        int32 device count of applied updates, advanced with the step unless it was skipped)."""
+        desc, rows, tiles, goff, boff, voff, eoff = self.opt_prepare(data, grad, mom, mom2, ema)
+        if ema is not None:
+            if ema_t is None or ema_t.dtype != torch.int32 or ema_t.device != data.device or ema_t.numel() < 1:
+                raise ValueError("opt_step: ema_t must be an int32 tensor on the arena's device")
+            if not 0.0 <= float(ema_decay) < 1.0:
+                raise ValueError(f"opt_step: ema_decay must be in [0, 1), got {ema_decay!r}")
         if gmul is not None and not (gmul.dtype == torch.float32 and gmul.device == data.device and gmul.numel() >= 1):
             raise ValueError("opt_step: gmul must be an fp32 tensor on the arena's device")
         if optimizer not in ("sgd", "adam", "adamw"):
@@ -264,8 +273,22 @@ class CANNetExecutor(ContextSchedule):
                         float(betas[1]), float(eps), float(weight_decay), int(optimizer == "adamw"), float(gscale),
                         step.data_ptr() if adam else 0, flags.data_ptr() if flags is not None else 0,
                         lr_dev.data_ptr() if lr_dev is not None else 0, self.dt, self._stream(),
-                        gmul.data_ptr() if gmul is not None else 0)
+                        gmul.data_ptr() if gmul is not None else 0,
+                        **(dict(eoff=eoff, ema_decay=float(ema_decay), ema_warmup=int(bool(ema_warmup)),
+                                ema_t=ema_t.data_ptr()) if ema is not None else {}))
         self._pack_version = self._weights_version()
+
+    def swap_weights(self, data: torch.Tensor, ema: torch.Tensor):
+        """Exchange the masters with the EMA arena in ONE launch over the optimizer's descriptor rows and write every
+        16-bit pack from the values that land in the master slots.  The parameters are views of ``data``, so the model
+        now holds (evaluates, saves) the other set of weights; no address changes, so captured graphs stay valid.  Two
+        swaps in a row are the identity, packs included."""
+        if not getattr(self, "_sgd_key", None) or self._sgd_key[0] != data.data_ptr():
+            raise RuntimeError("swap_weights: call opt_prepare on this arena first")
+        eoff = self._arena_off(data, ema, "EMA")
+        self.C.swap_pack(self._sgd_desc.data_ptr(), self._sgd_desc.shape[0], self._sgd_tiles, eoff, self.dt,
+                         self._stream())
+        self.mark_weights_updated()
 
     def norm_prepare(self, grad: torch.Tensor, slots: Sequence):
         """The gradient-norm pass's device table and scratch for this gradient arena (elementwise.hip
@@ -296,18 +319,26 @@ class CANNetExecutor(ContextSchedule):
                          flags.data_ptr() + 8 if flags is not None else 0, self._stream())
         return self.gn
 
+    @staticmethod
+    def _arena_off(data: torch.Tensor, other: torch.Tensor, what: str) -> int:
+        if other.shape != data.shape or other.dtype != torch.float32 or other.device != data.device or \
+                not other.is_contiguous():
+            raise ValueError(f"opt_step: the {what} arena must match the parameter arena")
+        if (other.data_ptr() - data.data_ptr()) % data.element_size():
+            raise ValueError("opt_step: arena offsets must be whole floats")
+        off = (other.data_ptr() - data.data_ptr()) // data.element_size()
+        if abs(off) < data.numel():
+            raise ValueError(f"opt_step: the {what} arena overlaps the parameter arena")
+        return off
+
     def opt_prepare(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor,
-                    mom2: Optional[torch.Tensor] = None):
-        """sgd_prepare (the descriptor rows are shared) + the second-moment arena's offset (0 without one)."""
+                    mom2: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None):
+        """sgd_prepare (the descriptor rows are shared) + the second-moment and the EMA arena's offsets (0 without
+        one)."""
         desc, rows, tiles, goff, boff = self.sgd_prepare(data, grad, mom)
-        voff = 0
-        if mom2 is not None:
-            if mom2.shape != data.shape or mom2.dtype != torch.float32 or mom2.device != data.device:
-                raise ValueError("opt_step: the second-moment arena must match the parameter arena")
-            if (mom2.data_ptr() - data.data_ptr()) % data.element_size():
-                raise ValueError("opt_step: arena offsets must be whole floats")
-            voff = (mom2.data_ptr() - data.data_ptr()) // data.element_size()
-        return desc, rows, tiles, goff, boff, voff
+        voff = self._arena_off(data, mom2, "second-moment") if mom2 is not None else 0
+        eoff = self._arena_off(data, ema, "EMA") if ema is not None else 0
+        return desc, rows, tiles, goff, boff, voff, eoff
 
     def mark_weights_updated(self):
         """Called by the fused optimizer after it has re-packed (keeps versions in sync)."""

@@ -236,6 +236,31 @@ def _(param, exp_avg, exp_avg_sq, grad, step, lr, beta1=0.9, beta2=0.999, eps=1e
     return None
 
 
+@torch.library.custom_op(f"{_LIB}::ema_", mutates_args=("ema",))
+def ema_(ema: torch.Tensor, param: torch.Tensor, decay: float, warmup: bool = True, step: int = 1) -> None:
+    """ema += w (param - ema), w = float32(1 - d), d = min(decay, (1 + n) / (10 + n)) with ``warmup`` (n = step - 1,
+    ``step`` the 1-based update of this call), d = decay without: the native step's EMA update (elementwise.hip
+    ema_kernel, any size and alignment), bit for bit ``C.ema``."""
+    for t, name in ((ema, "ema"), (param, "param")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{name} must be a contiguous fp32 GPU tensor")
+    if ema.numel() != param.numel():
+        raise ValueError("ema / param sizes differ")
+    if not 0.0 <= decay < 1.0:
+        raise ValueError("decay must be in [0, 1)")
+    if step < 1:
+        raise ValueError("step is the 1-based update of this call")
+    if ema.numel() == 0:
+        return
+    _ext.require().ema(ema.data_ptr(), param.data_ptr(), ema.numel(), float(decay), int(bool(warmup)), int(step), 0, 0,
+                       _ext.stream_ptr(ema.device))
+
+
+@ema_.register_fake
+def _(ema, param, decay, warmup=True, step=1):
+    return None
+
+
 class Conv2dNHWC(nn.Module):
     """nn.Conv2d(ci, co, k, padding=dilation*(k//2), dilation=dilation) [+ ReLU] on NHWC 16-bit activations, run
     by the native MFMA kernels (``torch.ops.cannet.conv2d_nhwc``).  Parameters are fp32 in the PyTorch layout, so

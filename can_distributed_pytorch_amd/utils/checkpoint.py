@@ -7,8 +7,9 @@
   nothing).  Loading uses ``weights_only=True``: nothing in the file executes.
 * ``save_train_state`` / ``load_train_state``: exact resume (weights, SGD
   momentum or Adam moments — native arenas or torch optimizer state —, epoch, min_mae,
-  min_epoch, the native stepper's loss scale / lr / step count, and the
-  torch CPU+CUDA, numpy and Python RNG streams) — the reference has none.
+  min_epoch, the native stepper's loss scale / lr / step count, the EMA of
+  the parameters when one is kept, and the torch CPU+CUDA, numpy and Python
+  RNG streams) — the reference has none.
 """
 from __future__ import annotations
 
@@ -75,13 +76,16 @@ def _set_rng_state(st: dict) -> None:
 def save_train_state(path: str, model, momentum: Optional[torch.Tensor], epoch: int, min_mae: float,
                      extra: Optional[dict] = None, optimizer=None, min_epoch: int = 0,
                      stepper_state: Optional[dict] = None, momentum2: Optional[torch.Tensor] = None,
-                     optimizer_name: Optional[str] = None) -> None:
+                     optimizer_name: Optional[str] = None, ema: Optional[dict] = None, ema_steps: int = 0,
+                     ema_decay: float = 0.0) -> None:
     """Everything an uninterrupted run carries into the next epoch: weights, the momentum (native arena, or
     the torch optimizer's state_dict), epoch / min_mae / min_epoch, the native stepper's device state (fp16 loss
     scale, lr, step count) and every RNG stream.  The data order needs no state: DistributedSampler is a
     function of (seed, epoch) and the flip of CrowdDataset one of (seed, epoch, index).  Adam / AdamW on the native
     arena: ``momentum`` is the first moment, ``momentum2`` the second; ``optimizer_name`` ("sgd" / "adam" / "adamw")
-    is checked on load."""
+    is checked on load.  ``ema``: the parameters' moving average as {parameter name: tensor} (a stepper's
+    ``ema_state()["ema"]``) with its update count and decay; written only when given, so a run without EMA writes
+    the file it wrote before."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     state = {
         "model": {k: v.detach().cpu() for k, v in _unwrap(model).state_dict().items()},
@@ -98,6 +102,10 @@ def save_train_state(path: str, model, momentum: Optional[torch.Tensor], epoch: 
     }
     if extra:
         state["extra"] = extra
+    if ema is not None:
+        state["ema"] = {k: v.detach().cpu() for k, v in ema.items()}
+        state["ema_steps"] = int(ema_steps)
+        state["ema_decay"] = float(ema_decay)
     tmp = path + ".tmp"
     torch.save(state, tmp)
     os.replace(tmp, path)
@@ -107,7 +115,8 @@ def load_train_state(path: str, model, momentum: Optional[torch.Tensor] = None, 
                      restore_rng: bool = True, momentum2: Optional[torch.Tensor] = None,
                      optimizer_name: Optional[str] = None) -> dict:
     """Restores what save_train_state wrote (weights_only load: nothing in the file executes).  Returns
-    {"epoch", "min_mae", "min_epoch", "stepper"}.  ``optimizer_name``: the optimizer of the resuming run; a state
+    {"epoch", "min_mae", "min_epoch", "stepper", "ema", "ema_steps", "ema_decay"} (``ema`` None for a state without
+    one; the caller hands it to the stepper's ``load_ema_state``).  ``optimizer_name``: the optimizer of the resuming run; a state
     written by another one (a state without the key is an SGD state) raises instead of reusing its buffers."""
     st = torch.load(path, map_location="cpu", weights_only=True)
     saved = st.get("optimizer_name") or ("sgd" if st.get("momentum2") is None else "adam")
@@ -126,7 +135,8 @@ def load_train_state(path: str, model, momentum: Optional[torch.Tensor] = None, 
     if restore_rng and st.get("rng") is not None:
         _set_rng_state(st["rng"])
     return {"epoch": int(st["epoch"]), "min_mae": float(st["min_mae"]), "min_epoch": int(st.get("min_epoch", 0)),
-            "stepper": st.get("stepper")}
+            "stepper": st.get("stepper"), "ema": st.get("ema"), "ema_steps": int(st.get("ema_steps", 0)),
+            "ema_decay": float(st.get("ema_decay", 0.0))}
 
 
 def load_checkpoint_dict(model, sd, strict: bool = True):

@@ -10,7 +10,10 @@ Kernel arms: one CANNetExecutor arena; the arms alternate within the process (``
 back-to-back launches per arm between two device events).  Bytes moved per launch are counted here: masters read +
 written, gradients read, each optimizer state arena read + written, the packs written.  A fourth, diagnostic arm runs
 the stand-alone Adam kernel over the same arena (the same arithmetic as a plain float4 stream, without the LDS transpose
-and the packs).  One JSON line per arm is printed and appended to ``--out``."""
+and the packs).  The EMA arms (``sgd_ema``, ``adam_ema``: the same launches with the EMA arena updated inside them;
+``ema_flat``: the stand-alone EMA kernel, which re-reads the masters) run interleaved with the others; each EMA arena adds
+one read and one write of the arena to the count.  ``--whole-step`` runs SGD and Adam with and without EMA.  One JSON
+line per arm is printed and appended to ``--out``."""
 from __future__ import annotations
 
 import argparse
@@ -49,6 +52,9 @@ def kernel_arms(args):
     arena.grad.normal_()
     mom, mom2 = torch.zeros_like(arena.data), torch.zeros_like(arena.data)
     t = torch.zeros(1, dtype=torch.int32, device=dev)
+    ema = arena.data.clone()
+    et = torch.zeros(1, dtype=torch.int32, device=dev)
+    ekw = dict(ema=ema, ema_t=et, ema_decay=0.999, ema_warmup=True)
     flags = torch.zeros(4, device=dev)
     lr_dev = torch.full((1,), 1e-9, device=dev)
     ex.refresh_packs(force=True)
@@ -59,8 +65,8 @@ def kernel_arms(args):
     nf = arena.data.numel()
     stream = torch.cuda.current_stream().cuda_stream
 
-    def fused_bytes(states):
-        return 4 * n * (2 + 1 + 2 * states) + pack_bytes
+    def fused_bytes(states, ema_arenas=0):
+        return 4 * n * (2 + 1 + 2 * states + 2 * ema_arenas) + pack_bytes
 
     # arm: (launch, bytes moved, device launches per call, note)
     arms = {
@@ -74,6 +80,15 @@ def kernel_arms(args):
                                         nf, 1e-9, 0.9, 0.999, 1e-8, 0.0, 0, 1.0, 0, t.data_ptr(), flags.data_ptr(),
                                         lr_dev.data_ptr(), stream), 4 * nf * 7, 2,
                       "stand-alone adam_kernel over the arena, no packs; includes the step-count launch"),
+        "sgd_ema": (lambda: ex.opt_step(arena.data, arena.grad, mom, 1e-9, 1.0, optimizer="sgd", **ekw, **common),
+                    fused_bytes(1, 1), 2, "includes the one-thread count launch"),
+        "adam_ema": (lambda: ex.opt_step(arena.data, arena.grad, mom, 1e-9, 1.0, optimizer="adam", mom2=mom2, step=t,
+                                         **ekw, **common), fused_bytes(2, 1), 2,
+                     "includes the one-thread count launch (both counts in one)"),
+        # the two-launch alternative's second launch: masters re-read, EMA read + written
+        "ema_flat": (lambda: ex.C.ema(ema.data_ptr(), arena.data.data_ptr(), nf, 0.999, 1, 0, et.data_ptr(),
+                                      flags.data_ptr(), stream), 4 * nf * 3, 2,
+                     "stand-alone ema_kernel over the arena; includes the count launch"),
     }
     for fn, *_ in arms.values():
         for _ in range(args.warmup):
@@ -94,7 +109,7 @@ def kernel_arms(args):
         v = sorted(ms[name])
         med = v[len(v) // 2]
         emit({"kind": "optimizer_kernel", "arm": name, "dtype": args.dtype, "params": n, "bytes": nbytes,
-              "pack_bytes": pack_bytes if name != "adam_flat" else 0, "calls": args.rounds * args.launches,
+              "pack_bytes": pack_bytes if not name.endswith("_flat") else 0, "calls": args.rounds * args.launches,
               "device_launches_per_call": per_call, "us_median": round(med * 1e3, 2),
               "us_min": round(v[0] * 1e3, 2), "us_max": round(v[-1] * 1e3, 2),
               "tb_per_s": round(nbytes / (med * 1e-3) / 1e12, 3), "note": note}, args.out)
@@ -107,9 +122,11 @@ def whole_step(args):
     for batch in (8, 1):
         img, gt = make_synthetic_batch(batch, 768, 1024, seed=0, device=dev)
         st = {}
-        for name, lr in (("sgd", 1e-7), ("adam", 1e-5)):
+        for name, lr, ema in (("sgd", 1e-7, 0.0), ("adam", 1e-5, 0.0), ("sgd_ema", 1e-7, 0.999),
+                              ("adam_ema", 1e-5, 0.999)):
             torch.manual_seed(0)
-            st[name] = NativeStepper(dev, dtype=args.dtype, lr=lr, batch=batch, graph=False, optimizer=name)
+            st[name] = NativeStepper(dev, dtype=args.dtype, lr=lr, batch=batch, graph=False,
+                                     optimizer=name.split("_")[0], ema_decay=ema)
             for _ in range(args.warmup):
                 st[name].step(img, gt)
         torch.cuda.synchronize()

@@ -17,6 +17,7 @@ a resumable ``checkpoints/last_state.pth``, JSONL metrics.
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -62,6 +63,13 @@ def clip_norm(v):
     x = float(v)
     if not x >= 0:
         raise argparse.ArgumentTypeError(f"--clip-grad-norm must be >= 0 (0 = off, inf = measure only), got {v!r}")
+    return x
+
+
+def ema_decay(v):
+    x = float(v)
+    if not 0.0 <= x < 1.0:
+        raise argparse.ArgumentTypeError(f"--ema-decay must be in [0, 1) (0 = off), got {v!r}")
     return x
 
 
@@ -112,6 +120,13 @@ def build_parser():
                    help="clip the global 2-norm of the (accumulated, averaged) gradient to this value ahead of the "
                         "optimizer, torch.nn.utils.clip_grad_norm_'s rule; 0 (default) = off, inf = measure the norm "
                         "only (logged as grad_norm)")
+    p.add_argument("--ema-decay", type=ema_decay, default=0.0,
+                   help="keep an exponential moving average of the weights with this decay and evaluate / checkpoint "
+                        "it instead of the raw weights (epoch_N.pth then holds the average, last_state.pth the raw "
+                        "weights plus the average); usual range 0.999-0.9999; 0 (default) = off")
+    p.add_argument("--ema-warmup", type=str2bool, default=True,
+                   help="with --ema-decay: use min(decay, (1 + n) / (10 + n)) at the n-th update, so the average "
+                        "follows the weights early on")
     p.add_argument("--beta1", type=float, default=0.9, help="Adam / AdamW first-moment decay")
     p.add_argument("--beta2", type=float, default=0.999, help="Adam / AdamW second-moment decay")
     p.add_argument("--eps", type=float, default=1e-8, help="Adam / AdamW epsilon")
@@ -264,7 +279,8 @@ def main(args):
     native = args.impl == "hip" and args.dtype != "fp32"
     opt = dict(optimizer=args.optimizer, momentum=args.momentum, weight_decay=args.weight_decay,
                betas=(args.beta1, args.beta2), eps=args.eps, accum_steps=args.accum_steps,
-               clip_grad_norm=args.clip_grad_norm)
+               clip_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+    ema_on = args.ema_decay > 0
     if native:
         stepper = build_trainer(impl="hip", dtype=args.dtype, device=device, world=world, lr=base_lr, graph=graph,
                                 model=model, bucket_mb=args.bucket_mb, comm_ctas=args.comm_ctas,
@@ -279,6 +295,7 @@ def main(args):
         if world > 1:
             for p in stepper.model.parameters():
                 dist.broadcast(p.data, src=0)
+            stepper.ema_start()                      # the average starts from the weights as broadcast
         net = stepper.net
         momentum = momentum2 = None
 
@@ -290,6 +307,11 @@ def main(args):
         start_epoch, min_mae, min_epoch = rs["epoch"] + 1, rs["min_mae"], rs["min_epoch"]
         if native:
             stepper.load_resume_state(rs["stepper"])
+        if ema_on:
+            if not stepper.load_ema_state(rs["ema"], rs["ema_steps"]) and rank == 0:
+                print(f"[resume: {args.resume} has no EMA; the average starts from the loaded weights at n = 0]")
+        elif rs["ema"] is not None and rank == 0:
+            print(f"[resume: {args.resume} holds an EMA of the weights; ignored (--ema-decay 0)]")
 
     from can_distributed_pytorch_amd.engine.train_eval import train_one_epoch_native, evaluate, train_one_epoch
     import math
@@ -308,29 +330,39 @@ def main(args):
                                                log_every=max(1, args.log_every), prep=train_prep if raw else prep)
         else:
             mean_loss = train_one_epoch(net, stepper.opt, train_loader, device, epoch,
-                                        accum_steps=args.accum_steps, clip_grad_norm=args.clip_grad_norm)
+                                        accum_steps=args.accum_steps, clip_grad_norm=args.clip_grad_norm,
+                                        **(dict(on_step=stepper.ema_update) if ema_on else {}))
         t_train = time.perf_counter() - t0
-        if (epoch + 1) % args.eval_every == 0 or epoch == args.epochs - 1:
-            mae_sum = evaluate(net, test_loader, device, epoch, show_images=args.show and rank == 0,
-                               use_wandb=use_wandb, out_dir=os.path.join(args.checkpoint_dir, "temp"), prep=prep)
-        else:
-            mae_sum = float("nan")
+        # EMA on: evaluation, the overlay PNGs and the best-MAE checkpoint see the averaged weights (every rank swaps)
+        averaged = stepper.ema_weights if ema_on else contextlib.nullcontext
+        with averaged():
+            if (epoch + 1) % args.eval_every == 0 or epoch == args.epochs - 1:
+                mae_sum = evaluate(net, test_loader, device, epoch, show_images=args.show and rank == 0,
+                                   use_wandb=use_wandb, out_dir=os.path.join(args.checkpoint_dir, "temp"), prep=prep)
+            else:
+                mae_sum = float("nan")
+            mean_mae = mae_sum / test_sampler.total_size      # padded size, reference parity (Q6)
+            if rank == 0 and mean_mae < min_mae:
+                min_mae, min_epoch = mean_mae, epoch
+                save_checkpoint(stepper.model, os.path.join(args.checkpoint_dir, f"epoch_{epoch}.pth"))
         if args.check_sync_every and (epoch + 1) % args.check_sync_every == 0 and world > 1:
             from can_distributed_pytorch_amd.parallel.consistency import check_replicas_consistent, check_comm_health
             if native:
                 check_comm_health(stepper.reducer)
                 check_replicas_consistent(stepper.arena.data)
+                if ema_on:
+                    check_replicas_consistent(stepper.ema)
             else:
                 check_replicas_consistent(torch.cat([p.detach().reshape(-1) for p in stepper.model.parameters()]))
+                if ema_on:
+                    check_replicas_consistent(torch.cat([e.reshape(-1) for e in stepper.ema_state()["ema"].values()]))
         if rank == 0:
-            mean_mae = mae_sum / test_sampler.total_size      # padded size, reference parity (Q6)
-            if mean_mae < min_mae:
-                min_mae, min_epoch = mean_mae, epoch
-                save_checkpoint(stepper.model, os.path.join(args.checkpoint_dir, f"epoch_{epoch}.pth"))
+            es = stepper.ema_state() if ema_on else None
             save_train_state(os.path.join(args.checkpoint_dir, "last_state.pth"), stepper.model, momentum, epoch,
                              min_mae, optimizer=None if native else stepper.opt, min_epoch=min_epoch,
                              stepper_state=stepper.resume_state() if native else None, momentum2=momentum2,
-                             optimizer_name=args.optimizer)
+                             optimizer_name=args.optimizer,
+                             **(dict(ema=es["ema"], ema_steps=es["steps"], ema_decay=args.ema_decay) if es else {}))
             lr_now = stepper.lr if native else stepper.opt.param_groups[0]["lr"]
             per_item = args.crops_per_image if args.crop_size is not None else 1
             ips = len(train_loader) * args.batch_size * per_item * world / max(t_train, 1e-9)
@@ -341,7 +373,8 @@ def main(args):
                     train_imgs_per_s=ips, train_s=t_train, train_mpix_per_s=st.get("mpix_per_s"),
                     train_loop_imgs_per_s=st.get("imgs_per_s"), batch_size=args.batch_size, world=world,
                     **(dict(crop_size=list(args.crop_size), crops_per_image=args.crops_per_image,
-                            eval_batch_size=test_loader.batch_size) if args.crop_size is not None else {}))
+                            eval_batch_size=test_loader.batch_size) if args.crop_size is not None else {}),
+                    **(dict(ema_decay=args.ema_decay) if ema_on else {}))
             if use_wandb:
                 wandb_log(loss=mean_loss, mae=mean_mae, lr=lr_now)
         barrier()
