@@ -123,6 +123,12 @@ int can_preprocess_batch(const void* imgs, const float* dens, const long long* d
 // device and (desc_host) on the host, where every window is checked against its image and img_bytes before the launch
 int can_preprocess_crop(const void* imgs, long long img_bytes, const long long* desc, const long long* desc_host,
                         int n, void* x4, int CH, int CW, int ds, int dt, void* stream);
+// random-scale crop batch, one launch: as can_preprocess_crop with slot 7 of a descriptor = (sh << 32) | sw, the extent
+// of the window at (y0, x0) that is resampled (cv2 INTER_LINEAR, taps clamped inside the window) to CH x CW; refuses
+// what can_preprocess_crop refuses, a window that is empty or leaves its image, and sh, sw beyond [CH/4, 4 CH], [CW/4, 4 CW]
+int can_preprocess_crop_scaled(const void* imgs, long long img_bytes, const long long* desc,
+                               const long long* desc_host, int n, void* x4, int CH, int CW, int ds, int dt,
+                               void* stream);
 // synthetic batch: full-res densities [n][H][W] + coarse noise [n][3][H/16][W/16] -> x4 NHWC4, gt [n][H/8][W/8]
 int can_synth_render(const float* dens, const float* noise, float* dmax, void* x4, float* gt, int n, int H, int W,
                      int dt, void* stream);

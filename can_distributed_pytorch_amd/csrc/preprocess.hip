@@ -164,6 +164,57 @@ __global__ void __launch_bounds__(256) preprocess_crop_kernel(const unsigned cha
   }
 }
 
+// Random-scale crop batch in ONE launch: desc[n] = {image byte offset, H0, W0, C, flip, y0, x0, (sh << 32) | sw}.
+// Output sample n = the window [y0, y0+sh) x [x0, x0+sw) of its image resampled to CH x CW by the cv2 INTER_LINEAR
+// rule (lin_tap relative to the window, taps clamped inside it; column taps mirrored within the window when
+// flipped), normalised in preprocess_batch_kernel's operation order.  No padding: the whole crop is valid.  It reads
+// only bytes of the window.  For sh == CH, sw == CW every fraction is exactly 0 and the blend returns the pixel
+// itself, so the output is bitwise preprocess_crop_kernel's.  A thread writes two adjacent NHWC4 pixels as one
+// 16-byte store (CW is even).
+template <int DT>
+__global__ void __launch_bounds__(256) preprocess_crop_scaled_kernel(const unsigned char* __restrict__ imgs,
+                                                                     const long long* __restrict__ desc,
+                                                                     uint4* __restrict__ x4, int CH, int CW) {
+  const long long* d = desc + (size_t)blockIdx.y * 8;
+  const int W0 = (int)d[2], C = (int)d[3], flip = (int)d[4], y0 = (int)d[5], x0 = (int)d[6];
+  const int sh = (int)(d[7] >> 32), sw = (int)(d[7] & 0xffffffffll);
+  const unsigned char* win = imgs + d[0] + ((size_t)y0 * W0 + x0) * C;      // the window's first pixel
+  const size_t pitch = (size_t)W0 * C;
+  const float sy = (float)sh / (float)CH, sx = (float)sw / (float)CW;
+  const int half = CW / 2;
+  uint4* out = x4 + (size_t)blockIdx.y * CH * half;
+  const float m[3] = {0.485f, 0.456f, 0.406f}, is[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < CH * half; i += gridDim.x * 256) {
+    const int oy = i / half, ox = (i % half) * 2;
+    int ya, yb;
+    float fy;
+    lin_tap(oy, sy, sh, ya, yb, fy);
+    const unsigned char* ra = win + (size_t)ya * pitch;
+    const unsigned char* rb = win + (size_t)yb * pitch;
+    unsigned int w[4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      int xa, xb;
+      float fx;
+      lin_tap(ox + p, sx, sw, xa, xb, fx);
+      if (flip) { xa = sw - 1 - xa; xb = sw - 1 - xb; }      // flip BEFORE the resize: mirror within the window
+      const size_t oa = (size_t)xa * C, ob = (size_t)xb * C;
+      float v[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int cc = (C == 1) ? 0 : c;
+        const float a = ra[oa + cc], b = ra[ob + cc];
+        const float e0 = rb[oa + cc], e1 = rb[ob + cc];
+        const float top = a + (b - a) * fx, bot = e0 + (e1 - e0) * fx;
+        v[c] = ((top + (bot - top) * fy) * (1.f / 255.f) - m[c]) * is[c];
+      }
+      w[2 * p] = pack2<DT>(v[0], v[1]);
+      w[2 * p + 1] = pack2<DT>(v[2], 0.f);
+    }
+    out[i] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Synthetic crowd batch on the GPU (train.py --synthetic / bench data; data/synthetic.py is the CPU
 // reference of the same recipe): per image, head points (host RNG, tiny) -> fixed-sigma Gaussian
@@ -266,6 +317,33 @@ extern "C" int can_preprocess_crop(const void* imgs, long long img_bytes, const 
   if (bx > 512) bx = 512;
   CAN_LAUNCH_DT(dt, preprocess_crop_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream,
                 (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW, ds);
+  return (int)hipGetLastError();
+}
+
+// can_preprocess_crop's checks, plus the window extents of slot 7: inside the image, and within a factor 4 of the crop
+// either way (the range of --crop-scale, with the rounding of the extents).
+extern "C" int can_preprocess_crop_scaled(const void* imgs, long long img_bytes, const long long* desc,
+                                          const long long* desc_host, int n, void* x4, int CH, int CW, int ds, int dt,
+                                          void* stream) {
+  using namespace can;
+  if (n <= 0 || n > 65535 || ds <= 0 || CH <= 0 || CW <= 0 || CH % ds || CW % ds || CW % 2) return -2;
+  if ((long long)CH * CW > 0x7fffffff) return -2;
+  if (imgs == nullptr || desc == nullptr || desc_host == nullptr || x4 == nullptr || ((uintptr_t)x4 & 15)) return -2;
+  for (int i = 0; i < n; ++i) {
+    const long long* d = desc_host + (size_t)i * 8;
+    const long long off = d[0], H0 = d[1], W0 = d[2], C = d[3], flip = d[4], y0 = d[5], x0 = d[6];
+    if (d[7] <= 1 || (C != 1 && C != 3 && C != 4) || (flip != 0 && flip != 1)) return -2;
+    const long long sh = d[7] >> 32, sw = d[7] & 0xffffffffll;
+    if (H0 <= 0 || W0 <= 0 || H0 > 0x7fffffff || W0 > 0x7fffffff) return -2;
+    if (off < 0 || off > img_bytes || H0 * W0 > (img_bytes - off) / C) return -2;
+    if (sh < 1 || sw < 1 || sh > H0 || sw > W0) return -2;
+    if (y0 < 0 || x0 < 0 || y0 > H0 - sh || x0 > W0 - sw) return -2;
+    if (sh > 4ll * CH || sw > 4ll * CW || CH > 4 * sh || CW > 4 * sw) return -2;
+  }
+  int bx = (CH * (CW / 2) + 255) / 256;
+  if (bx > 512) bx = 512;
+  CAN_LAUNCH_DT(dt, preprocess_crop_scaled_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream,
+                (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW);
   return (int)hipGetLastError();
 }
 

@@ -18,6 +18,8 @@ worker processes, travels with the index (``EpochTaggedSampler``).
 random windows of that size of the one decoded image, each with its own
 offset and flip drawn by ``crop_draw`` from (seed, epoch, index, k), zero-padded
 where the image is smaller than the crop (README, "Random-crop training").
+``crop_scale=(lo, hi)`` adds a random scale per crop (``scale_draw``): a window of
+(ch, cw) / s is resampled to the crop, never padded (README, "Random-scale crops").
 ``SyntheticCrowdDataset`` provides the same item contract without files
 (benchmarks, tests, smoke runs).
 """
@@ -30,7 +32,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from .transforms import _axis_weights, prepare_pair
+from .transforms import _axis_weights, area_factor, prepare_pair, prepare_pair_scaled
 
 IMG_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".tif", ".tiff")
 _M64 = (1 << 64) - 1
@@ -64,6 +66,34 @@ def crop_draw(seed: int, epoch: int, index: int, k: int, ny: int, nx: int):
     return int(y0), int(x0), bool(_splitmix64(s ^ 3) >> 63)
 
 
+def scale_draw(seed: int, epoch: int, index: int, k: int, lo: float, hi: float) -> float:
+    """The scale of crop ``k`` of sample ``index`` in ``epoch``: log-uniform on [lo, hi], > 1 magnifies.  One more hash
+    of ``crop_draw``'s chain state, so it is as stateless (no dependence on K, workers or resumes) and leaves the
+    offset and flip draws what they are."""
+    s = _splitmix64(_splitmix64(_splitmix64(_splitmix64(seed & _M64) ^ (epoch & _M64)) ^ (index & _M64)) ^ (k & _M64))
+    u = (_splitmix64(s ^ 4) >> 11) / 2 ** 53
+    return float(min(hi, max(lo, lo * (hi / lo) ** u)))
+
+
+def check_crop_scale(lo, hi):
+    """(lo, hi) as floats, or ValueError: 0.25 <= lo <= hi <= 4 (the range the scaled crop kernel accepts)."""
+    lo, hi = float(lo), float(hi)
+    if not (0.0 < lo <= hi) or lo < 0.25 or hi > 4.0:
+        raise ValueError(f"crop scale range must satisfy 0.25 <= lo <= hi <= 4, got {lo},{hi}")
+    return lo, hi
+
+
+def scaled_window(h0: int, w0: int, ch: int, cw: int, s: float):
+    """(sh, sw): the source extent that scale ``s`` resamples to a (ch, cw) crop of an h0 x w0 image.  The scale is
+    raised to what makes the window fit (s_eff = max(s, ch/h0, cw/w0)): the crop is always fully valid, and an image
+    smaller than the crop is upsampled to fill it (the unscaled path pads it instead).  float64 on the host; the
+    kernel sees the integers only."""
+    s_eff = max(float(s), ch / h0, cw / w0)
+    sh = min(h0, max(1, int(np.floor(ch / s_eff + 0.5))))
+    sw = min(w0, max(1, int(np.floor(cw / s_eff + 0.5))))
+    return sh, sw
+
+
 def _pad_to(a: np.ndarray, h: int, w: int) -> np.ndarray:
     """Zero-pad the last two axes at the bottom / right to (h, w)."""
     if a.shape[-2:] == (h, w):
@@ -79,28 +109,40 @@ def crop_collate(batch):
     return torch.cat(imgs), torch.cat(gts)
 
 
+def _density_resize(dmap: np.ndarray, rows: int, cols: int, flip: bool) -> np.ndarray:
+    """Optional flip, then the cv2 INTER_LINEAR resize of a 2-D density map of any size to (rows, cols), float64."""
+    if dmap.ndim != 2:
+        raise ValueError(f"density must be a 2-D map, got shape {tuple(dmap.shape)}")
+    hd, wd = (int(v) for v in dmap.shape)
+    if (rows, cols) == (hd, wd):
+        return np.asarray(dmap, dtype=np.float64)[:, ::-1] if flip else np.asarray(dmap, dtype=np.float64)
+    # gather the rows the vertical taps use first (a memory-mapped map is read only there), then resize
+    y0, y1, fy = _axis_weights(hd, rows)
+    x0, x1, fx = _axis_weights(wd, cols)
+    if flip:                                 # flip before resize == mirrored column taps
+        x0, x1 = wd - 1 - x0, wd - 1 - x1
+    need = np.unique(np.concatenate([y0, y1]))
+    sub = np.asarray(dmap[need], dtype=np.float64)
+    pos = np.searchsorted(need, np.arange(hd))
+    r = sub[pos[y0]] * (1.0 - fy)[:, None] + sub[pos[y1]] * fy[:, None]
+    return r[:, x0] * (1.0 - fx)[None] + r[:, x1] * fx[None]
+
+
 def density_to_gt(dmap: np.ndarray, h: int, w: int, downsample: int, flip: bool) -> np.ndarray:
     """The density half of prepare_pair (model/CrowdDataset.py:48-62): optional flip, cv2 INTER_LINEAR resize of a
     density map of ANY size to (W//d, H//d) of the IMAGE's size (reference :60 resizes whatever map it loaded), x d^2.
     Returns fp32 [1, H//d, W//d]."""
-    if dmap.ndim != 2:
-        raise ValueError(f"density must be a 2-D map, got shape {tuple(dmap.shape)}")
-    hd, wd = (int(v) for v in dmap.shape)
-    rows, cols = h // downsample, w // downsample
-    if (rows, cols) == (hd, wd):
-        dm = np.asarray(dmap, dtype=np.float64)[:, ::-1] if flip else np.asarray(dmap, dtype=np.float64)
-    else:
-        # gather the rows the vertical taps use first (a memory-mapped map is read only there), then resize
-        y0, y1, fy = _axis_weights(hd, rows)
-        x0, x1, fx = _axis_weights(wd, cols)
-        if flip:                                 # flip before resize == mirrored column taps
-            x0, x1 = wd - 1 - x0, wd - 1 - x1
-        need = np.unique(np.concatenate([y0, y1]))
-        sub = np.asarray(dmap[need], dtype=np.float64)
-        pos = np.searchsorted(need, np.arange(hd))
-        r = sub[pos[y0]] * (1.0 - fy)[:, None] + sub[pos[y1]] * fy[:, None]
-        dm = r[:, x0] * (1.0 - fx)[None] + r[:, x1] * fx[None]
+    dm = _density_resize(dmap, h // downsample, w // downsample, flip)
     return (dm * (downsample * downsample))[None].astype(np.float32)
+
+
+def density_to_gt_scaled(dmap: np.ndarray, ch: int, cw: int, downsample: int, flip: bool) -> np.ndarray:
+    """The density half of prepare_pair_scaled: a density WINDOW of any extent (sh, sw) -> the ground truth of the
+    (ch, cw) sample it is resampled to, x (sh*sw) / cells (the area ratio, d^2 for an unscaled window).  Row-gathered
+    like density_to_gt.  Returns fp32 [1, ch//d, cw//d]."""
+    rows, cols = ch // downsample, cw // downsample
+    dm = _density_resize(dmap, rows, cols, flip).astype(np.float32)
+    return (dm * area_factor(dmap.shape[0], dmap.shape[1], rows, cols))[None]
 
 
 class EpochTaggedSampler:
@@ -137,7 +179,8 @@ def imread(path: str) -> np.ndarray:
 
 class CrowdDataset(Dataset):
     def __init__(self, img_root: str, gt_dmap_root: str, gt_downsample: int = 1, phase: str = "train",
-                 seed: Optional[int] = None, raw: bool = False, crop=None, crops_per_image: int = 1):
+                 seed: Optional[int] = None, raw: bool = False, crop=None, crops_per_image: int = 1,
+                 crop_scale=None):
         self.img_root = img_root
         self.gt_dmap_root = gt_dmap_root
         self.gt_downsample = max(1, int(gt_downsample))
@@ -161,6 +204,14 @@ class CrowdDataset(Dataset):
             if self.crops_per_image < 1:
                 raise ValueError(f"crops_per_image must be >= 1, got {crops_per_image}")
             self.crop = (ch, cw)
+        # crop_scale=(lo, hi): every crop resamples a window of (ch, cw) / s, s log-uniform on [lo, hi] (scale_draw)
+        self.crop_scale = None
+        if crop_scale is not None:
+            if crop is None:
+                raise ValueError("crop_scale needs crop=(ch, cw)")
+            lo_hi = check_crop_scale(*crop_scale)
+            if self.crop is not None:
+                self.crop_scale = lo_hi
 
     def __len__(self):
         return self.n_samples
@@ -208,6 +259,8 @@ class CrowdDataset(Dataset):
         if tuple(dmap.shape) != (h0, w0):
             raise ValueError(f"{name}: density map {tuple(dmap.shape)} differs from its image {(h0, w0)}: a crop "
                              "takes the same window of both")
+        if self.crop_scale is not None:
+            return self._scaled_crop_item(img, dmap, epoch, index)
         vh, vw = crop_window(h0, w0, ch, cw, d)
         draws = [crop_draw(self.seed, epoch, index, k, h0 - vh + 1, w0 - vw + 1) for k in range(K)]
         if self.raw:
@@ -224,6 +277,30 @@ class CrowdDataset(Dataset):
             ims.append(_pad_to(im, ch, cw))
             dms.append(_pad_to(dm, ch // d, cw // d))
         return torch.from_numpy(np.stack(ims)), torch.from_numpy(np.stack(dms))
+
+    def _scaled_crop_item(self, img: np.ndarray, dmap: np.ndarray, epoch: int, index: int):
+        """_crop_item with crop_scale: crop k resamples the window (y0, x0, sh, sw) = scaled_window of its scale_draw,
+        placed by crop_draw.  raw=False: the K prepare_pair_scaled pairs.  raw=True: (uint8 image, [K,1,ch/d,cw/d]
+        f32, int64 [K,5] of (y0, x0, flip, sh, sw)), the GPU resamples the windows (ops/preprocess.py)."""
+        d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
+        h0, w0 = img.shape[:2]
+        lo, hi = self.crop_scale
+        wins = []
+        for k in range(K):
+            sh, sw = scaled_window(h0, w0, ch, cw, scale_draw(self.seed, epoch, index, k, lo, hi))
+            y0, x0, fl = crop_draw(self.seed, epoch, index, k, h0 - sh + 1, w0 - sw + 1)
+            wins.append((y0, x0, int(fl), sh, sw))
+        if self.raw:
+            if img.dtype != np.uint8:
+                img = np.clip(np.asarray(img, dtype=np.float64) * (255.0 if img.dtype.kind == "f" else 1.0),
+                              0, 255).astype(np.uint8)
+            gts = np.stack([density_to_gt_scaled(dmap[y0:y0 + sh, x0:x0 + sw], ch, cw, d, bool(fl))
+                            for y0, x0, fl, sh, sw in wins])
+            return (torch.from_numpy(np.require(img, requirements=("C", "W"))), torch.from_numpy(gts),
+                    torch.tensor(wins, dtype=torch.int64))
+        pairs = [prepare_pair_scaled(img[y0:y0 + sh, x0:x0 + sw], dmap[y0:y0 + sh, x0:x0 + sw], ch, cw, d, bool(fl))
+                 for y0, x0, fl, sh, sw in wins]
+        return (torch.from_numpy(np.stack([p[0] for p in pairs])), torch.from_numpy(np.stack([p[1] for p in pairs])))
 
 
 class SyntheticCrowdDataset(Dataset):

@@ -80,3 +80,31 @@ def prepare_pair(img: np.ndarray, dmap: np.ndarray, downsample: int = 8, flip: b
     img = resize_linear(np.ascontiguousarray(img), cols * downsample, rows * downsample)
     dm = resize_linear(np.ascontiguousarray(dmap, dtype=np.float32), cols, rows) * (downsample * downsample)
     return normalize_chw(img), dm[None].astype(np.float32)
+
+
+def area_factor(sh: int, sw: int, rows: int, cols: int) -> np.float32:
+    """What a (sh, sw) density window resampled to (rows, cols) cells is multiplied by: source pixels per cell
+    (exactly d*d for an unscaled window of (rows*d, cols*d))."""
+    return np.float32((sh * sw) / (rows * cols))
+
+
+def prepare_pair_scaled(img: np.ndarray, dmap: np.ndarray, ch: int, cw: int, downsample: int = 8, flip: bool = False):
+    """prepare_pair for a source window of ANY extent (sh, sw) resampled to a (ch, cw) sample (random-scale crops):
+    flip within the window, cv2 INTER_LINEAR resize of the image to (cw, ch), normalise; density resized to
+    (cw/d, ch/d) x (sh*sw) / cells.  The taps clamp inside the window handed in, so the result is a function of its
+    bytes alone; for (sh, sw) == (ch, cw) it is prepare_pair's result bit for bit.  The density stays point-sampled
+    (module docstring): a shrunk window (sh > ch) samples every sh/(ch/d)-th pixel pair, coarser than the unscaled
+    rule.  Returns (img 3 x ch x cw f32, dmap 1 x ch/d x cw/d f32)."""
+    if downsample < 1 or ch <= 0 or cw <= 0 or ch % downsample or cw % downsample:
+        raise ValueError(f"sample {ch}x{cw} must be a positive multiple of the downsample {downsample}")
+    if tuple(dmap.shape) != tuple(img.shape[:2]):
+        raise ValueError(f"density window {tuple(dmap.shape)} differs from its image window {tuple(img.shape[:2])}")
+    img = gray_to_rgb(to_unit_float(img))
+    if flip:
+        img = img[:, ::-1]
+        dmap = dmap[:, ::-1]
+    sh, sw = img.shape[:2]
+    rows, cols = ch // downsample, cw // downsample
+    img = resize_linear(np.ascontiguousarray(img), cw, ch)
+    dm = resize_linear(np.ascontiguousarray(dmap, dtype=np.float32), cols, rows) * area_factor(sh, sw, rows, cols)
+    return normalize_chw(img), dm[None].astype(np.float32)

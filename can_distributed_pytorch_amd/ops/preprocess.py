@@ -10,7 +10,9 @@ in ONE uint8 buffer), the main process makes one pinned H2D copy of it and
 ONE kernel launch turns the batch into network inputs (``preprocess_packed``).
 ``preprocess_batch`` is the per-sample form (tests / variable-size use).
 ``PackedCollate(crop=(ch, cw))`` packs random-crop batches: every image once,
-one descriptor per crop, cut on the GPU by one launch of the crop kernel.
+one descriptor per crop, cut on the GPU by one launch of the crop kernel;
+with ``crop_scale=True`` every descriptor carries its window's extent and the
+scaled crop kernel resamples it to the crop.
 """
 from __future__ import annotations
 
@@ -71,10 +73,13 @@ class PackedCollate:
     brought each ground truth to 1/d resolution (flip and x d^2 included), so only the images are resized on the
     GPU.  Runs in the loader workers; pin_memory=True pins the buffer.  (Three separate pinned copies per batch were
     ~0.23 ms of host time per step at batch 1: profiles/r5/host/.)  crop=(ch, cw): the random-crop form for
-    CrowdDataset(raw=True, crop=...) items, see ``_call_crop``."""
+    CrowdDataset(raw=True, crop=...) items, see ``_call_crop``; crop_scale=True: its items carry scaled windows."""
 
-    def __init__(self, downsample: int = 8, crop=None):
+    def __init__(self, downsample: int = 8, crop=None, crop_scale=False):
         self.ds = downsample
+        self.crop_scale = bool(crop_scale)
+        if self.crop_scale and crop is None:
+            raise ValueError("crop_scale needs crop=(ch, cw)")
         self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
         if self.crop is not None and (min(self.crop) <= 0 or self.crop[0] % downsample or self.crop[1] % downsample):
             raise ValueError(f"crop {self.crop} must be a positive multiple of the downsample {downsample}")
@@ -83,21 +88,29 @@ class PackedCollate:
         """CrowdDataset(raw=True, crop=...) items (uint8 image, gts [K,1,ch/d,cw/d], windows [K,3] of (y0, x0, flip)):
         every image's bytes ONCE, the [B*K,1,ch/d,cw/d] ground truth and one descriptor per output sample,
         desc = (image byte offset, H0, W0, C, flip, y0, x0, 1) -- the K crops of an image share its offset.  The
-        meta tuple gains a sixth field, the number of images, which marks the pack as cropped."""
+        meta tuple gains a sixth field, the number of images, which marks the pack as cropped.
+        crop_scale: the windows are [K,5] of (y0, x0, flip, sh, sw), slot 7 of a descriptor is (sh << 32) | sw (never
+        the unscaled 1) and the meta tuple gains a seventh field, 1, which marks the pack as scaled."""
         ch, cw = self.crop
+        nw = 5 if self.crop_scale else 3
         imgs, gts, wins = zip(*batch)
         rows, ioff = [], 0
         for im, g, wn in zip(imgs, gts, wins):
             hh, ww = im.shape[:2]
             c = 1 if im.dim() == 2 else im.shape[2]
             if g.dim() != 4 or tuple(g.shape[1:]) != (1, ch // self.ds, cw // self.ds) or \
-                    tuple(wn.shape) != (g.shape[0], 3):
-                raise ValueError("cropped raw samples must carry ground truths [K, 1, ch/d, cw/d] and windows [K, 3]")
-            rows += [[ioff, hh, ww, c, fl, y0, x0, 1] for y0, x0, fl in wn.tolist()]
+                    tuple(wn.shape) != (g.shape[0], nw):
+                raise ValueError(f"cropped raw samples must carry ground truths [K, 1, ch/d, cw/d] and windows [K, {nw}]")
+            if self.crop_scale:
+                if int(wn[:, 3:].min()) < 1 or int(wn[:, 3:].max()) > 0x7fffffff:
+                    raise ValueError("scaled windows must have extents 1 <= sh, sw < 2^31")
+                rows += [[ioff, hh, ww, c, fl, y0, x0, (sh << 32) | sw] for y0, x0, fl, sh, sw in wn.tolist()]
+            else:
+                rows += [[ioff, hh, ww, c, fl, y0, x0, 1] for y0, x0, fl in wn.tolist()]
             ioff += hh * ww * c
         desc = torch.tensor(rows, dtype=torch.int64)
         buf, goff, doff = self._fill(imgs, ioff, torch.cat(gts).float().contiguous(), desc)
-        return buf, (desc.shape[0], ch, cw, goff, doff, len(imgs))
+        return buf, (desc.shape[0], ch, cw, goff, doff, len(imgs)) + ((1,) if self.crop_scale else ())
 
     @staticmethod
     def _fill(imgs, ioff, gt, desc):
@@ -136,14 +149,15 @@ class PackedCollate:
 
 
 def _unpack(packed):
-    """(buf, (n, Ho, Wo, gt_offset, desc_offset), cropped) of a PackedCollate output; a cropped pack's meta tuple
-    carries a sixth field (its number of images) and n counts output samples, one descriptor each."""
+    """(buf, (n, Ho, Wo, gt_offset, desc_offset), cropped, scaled) of a PackedCollate output; a cropped pack's meta
+    tuple carries a sixth field (its number of images) and n counts output samples, one descriptor each; a scaled
+    pack's carries a seventh, 1."""
     buf, meta = packed
     n, ho, wo, goff, doff = meta[:5]
-    if len(meta) not in (5, 6) or buf.dtype != torch.uint8 or buf.dim() != 1 or goff % 16 or doff % 16 or \
+    if len(meta) not in (5, 6, 7) or (len(meta) == 7 and meta[6] != 1) or buf.dtype != torch.uint8 or buf.dim() != 1 or goff % 16 or doff % 16 or \
             buf.numel() != doff + 64 * n:
         raise ValueError("packed batch: one uint8 buffer (images | fp32 ground truth | int64 descriptors)")
-    return buf, (n, ho, wo, goff, doff), len(meta) == 6
+    return buf, (n, ho, wo, goff, doff), len(meta) == 6, len(meta) == 7
 
 
 def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = torch.bfloat16,
@@ -153,7 +167,7 @@ def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = 
     compute stream then waits for it): a pinned copy queued behind the previous step's kernels on the compute stream
     held the host ~0.6 ms per step at batch 1 (profiles/r5/host/), one on an idle copy stream does not."""
     C = _ext.require()
-    buf, (n, ho, wo, goff, doff), cropped = _unpack(packed)
+    buf, (n, ho, wo, goff, doff), cropped, scaled = _unpack(packed)
     dev = torch.device(device)
     from .conv import dt_code
     if copy_stream is not None:
@@ -169,7 +183,10 @@ def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = 
     gtd = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
     ds = d[doff:].view(torch.int64).view(n, 8)
     x4 = torch.empty(n, ho, wo, 4, dtype=dtype, device=dev)
-    if cropped:
+    if scaled:
+        C.preprocess_crop_scaled(ib.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), ho, wo,
+                                 downsample, dt_code(dtype), _ext.stream_ptr(dev))
+    elif cropped:
         C.preprocess_crop(ib.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), ho, wo,
                           downsample, dt_code(dtype), _ext.stream_ptr(dev))
     else:
@@ -197,7 +214,7 @@ class AheadPrep:
     def issue(self, packed):
         from .conv import dt_code
         C = _ext.require()
-        buf, (n, ho, wo, goff, doff), cropped = _unpack(packed)
+        buf, (n, ho, wo, goff, doff), cropped, scaled = _unpack(packed)
         # the copy stream must not overwrite memory the compute stream's queued kernels may still read: wait for
         # what the compute stream has queued so far is NOT needed (fresh blocks of the copy stream's own pool), and
         # the hand-off below keeps the blocks out of that pool until the compute stream is done with them
@@ -208,7 +225,11 @@ class AheadPrep:
             ds = d[doff:].view(torch.int64).view(n, 8)
             x4 = torch.empty(n, ho, wo, 4, dtype=self.dtype, device=self.device)
             with _ext.launch_on(self.copy.cuda_stream):
-                if cropped:
+                if scaled:
+                    C.preprocess_crop_scaled(d.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n,
+                                             x4.data_ptr(), ho, wo, self.ds, dt_code(self.dtype),
+                                             _ext.stream_ptr(self.device))
+                elif cropped:
                     C.preprocess_crop(d.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), ho,
                                       wo, self.ds, dt_code(self.dtype), _ext.stream_ptr(self.device))
                 else:

@@ -83,6 +83,16 @@ def crop_size(v):
     return h, w
 
 
+def crop_scale(v):
+    try:
+        lo, hi = (float(x) for x in str(v).split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--crop-scale expects LO,HI, got {v!r}")
+    if not (0.0 < lo <= hi) or lo < 0.25 or hi > 4.0:
+        raise argparse.ArgumentTypeError(f"--crop-scale must satisfy 0.25 <= LO <= HI <= 4, got {v!r}")
+    return lo, hi
+
+
 def crop_count(v):
     n = int(v)
     if n < 1:
@@ -95,6 +105,8 @@ class _Parser(argparse.ArgumentParser):
         ns = super().parse_args(args, namespace)
         if ns.crop_size is not None and ns.synthetic:
             self.error("--crop-size crops decoded dataset images; it cannot be combined with --synthetic")
+        if ns.crop_scale is not None and ns.crop_size is None:
+            self.error("--crop-scale rescales the windows of --crop-size; give --crop-size as well")
         return ns
 
 
@@ -181,6 +193,11 @@ def build_parser():
                    help="with --crop-size: crops cut from every decoded image (one decode, one copy); a step sees "
                         "batch-size x this many samples and the loss is sum-reduced, so choose --lr as for that many "
                         "images (as with --accum-steps)")
+    p.add_argument("--crop-scale", type=crop_scale, default=None, metavar="LO,HI",
+                   help="with --crop-size: every crop draws a scale s log-uniformly on [LO, HI] (0.25 <= LO <= HI <= 4, "
+                        "e.g. 0.75,1.33) and resamples a window of the crop size / s to the crop (s > 1 magnifies), "
+                        "bilinearly, the density rescaled by the area ratio.  The window always fits: an image smaller "
+                        "than the crop is upsampled to fill it, not padded.  Default: off")
     p.add_argument("--log-every", type=int, default=20,
                    help="steps between the training records of --log-jsonl (each reads the loss back: a host sync)")
     return p
@@ -200,7 +217,8 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
     if crop is not None:
         # every training sample is a crop of one size; test images stay whole and of mixed size: batch 1
         from can_distributed_pytorch_amd.data.dataset import crop_collate
-        train_collate, eval_batch = (PackedCollate(crop=crop) if raw else crop_collate), 1
+        train_collate = PackedCollate(crop=crop, crop_scale=args.crop_scale is not None) if raw else crop_collate
+        eval_batch = 1
     if args.synthetic:
         h, w = (int(v) for v in args.synthetic.lower().split("x"))
         train_ds = SyntheticCrowdDataset(args.synthetic_n, h, w, seed=args.seed)
@@ -209,7 +227,8 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
         r = args.data_root
         train_ds = CrowdDataset(os.path.join(r, "train_data", "images"), os.path.join(r, "train_data", "ground_truth"),
                                 gt_downsample=8, phase="train", seed=args.seed, raw=raw, crop=crop,
-                                crops_per_image=args.crops_per_image if crop is not None else 1)
+                                crops_per_image=args.crops_per_image if crop is not None else 1,
+                                crop_scale=args.crop_scale)
         test_ds = CrowdDataset(os.path.join(r, "test_data", "images"), os.path.join(r, "test_data", "ground_truth"),
                                gt_downsample=8, phase="test", raw=raw)
     train_sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed)
@@ -374,6 +393,7 @@ def main(args):
                     train_loop_imgs_per_s=st.get("imgs_per_s"), batch_size=args.batch_size, world=world,
                     **(dict(crop_size=list(args.crop_size), crops_per_image=args.crops_per_image,
                             eval_batch_size=test_loader.batch_size) if args.crop_size is not None else {}),
+                    **(dict(crop_scale=list(args.crop_scale)) if args.crop_scale is not None else {}),
                     **(dict(ema_decay=args.ema_decay) if ema_on else {}))
             if use_wandb:
                 wandb_log(loss=mean_loss, mae=mean_mae, lr=lr_now)
