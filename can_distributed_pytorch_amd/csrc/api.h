@@ -116,15 +116,18 @@ int can_density_map(const float* pts, int n, int H, int W, float* sigma_ws, floa
 // preprocess.hip
 int can_preprocess_image(const void* img, int H0, int W0, int C, int flip, void* out, int Ho, int Wo, int dt,
                          void* stream);
-// one launch per batch: packed uint8 images / fp32 densities, desc [n][8] int64 (device)
+// resize batch, one launch: packed uint8 images, desc [n][8] int64 (device) = {image byte offset, H0, W0, C, flip, 0, 0,
+// 0}, every image resampled whole to Ho x Wo (Wo even, x4 16-byte aligned).  Images only: a pack carries its ground
+// truth at 1/ds resolution already, so dens and gt must be null; -2 for a non-null one, before any launch.
 int can_preprocess_batch(const void* imgs, const float* dens, const long long* desc, int n, void* x4, float* gt,
                          int Ho, int Wo, int ds, int dt, void* stream);
 // random-crop batch, one launch, no resize: desc [n][8] int64 = {image byte offset, H0, W0, C, flip, y0, x0, 1} on the
 // device and (desc_host) on the host, where every window is checked against its image and img_bytes before the launch
 int can_preprocess_crop(const void* imgs, long long img_bytes, const long long* desc, const long long* desc_host,
                         int n, void* x4, int CH, int CW, int ds, int dt, void* stream);
-// random-scale crop batch, one launch: as can_preprocess_crop with slot 7 of a descriptor = (sh << 32) | sw, the extent
-// of the window at (y0, x0) that is resampled (cv2 INTER_LINEAR, taps clamped inside the window) to CH x CW; refuses
+// random-scale crop batch, one launch of can_preprocess_batch's kernel: as can_preprocess_crop with slot 7 of a
+// descriptor = (sh << 32) | sw, the extent of the window at (y0, x0) that is resampled (cv2 INTER_LINEAR, taps clamped
+// inside the window) to CH x CW; refuses
 // what can_preprocess_crop refuses, a window that is empty or leaves its image, and sh, sw beyond [CH/4, 4 CH], [CW/4, 4 CW]
 int can_preprocess_crop_scaled(const void* imgs, long long img_bytes, const long long* desc,
                                const long long* desc_host, int n, void* x4, int CH, int CW, int ds, int dt,

@@ -8,6 +8,9 @@
 // no anti-aliasing.  Here both run on the GPU straight from the decoded uint8
 // image and write the first conv layer's NHWC4 bf16 layout (channel 3 = 0),
 // so the host only decodes JPEGs.
+//
+// Every kernel below is built from one set of helpers: lin_tap (the tap rule), blend4 (the four-tap blend),
+// imagenet / normalise / pack_px (ImageNet constants, x 1/255, NHWC4 words), resample_px (a whole pixel) and load_desc.
 #include "common.h"
 
 namespace can {
@@ -22,12 +25,59 @@ __device__ __forceinline__ void lin_tap(int o, float scale, int in, int& i0, int
   i1 = min(x0 + 1, in - 1);
 }
 
+// taps a b (top row) / d e (bottom row), left to right
+__device__ __forceinline__ float blend4(float a, float b, float d, float e, float fx, float fy) {
+  const float top = a + (b - a) * fx, bot = d + (e - d) * fx;
+  return top + (bot - top) * fy;
+}
+
+// channel c of a pixel in [0, 1] -> ImageNet-normalised (the one copy of the constants)
+__device__ __forceinline__ float imagenet(float v, int c) {
+  const float m[3] = {0.485f, 0.456f, 0.406f}, is[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
+  return (v - m[c]) * is[c];
+}
+
+// the same of a pixel on the uint8 scale [0, 255]
+__device__ __forceinline__ float normalise(float v, int c) { return imagenet(v * (1.f / 255.f), c); }
+
+// one NHWC4 pixel (channel 3 = 0) as two 16-bit pairs
+template <int DT>
+__device__ __forceinline__ uint2 pack_px(const float (&v)[3]) {
+  return make_uint2(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], 0.f));
+}
+
+// One output pixel of a uint8 image: tap rows ra / rb, tap pixels at byte offsets oa / ob of a row; gray (C == 1)
+// feeds all three channels.
+template <int DT>
+__device__ __forceinline__ uint2 resample_px(const unsigned char* ra, const unsigned char* rb, size_t oa, size_t ob,
+                                             int C, float fx, float fy) {
+  float v[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int cc = (C == 1) ? 0 : c;
+    v[c] = normalise(blend4(ra[oa + cc], ra[ob + cc], rb[oa + cc], rb[ob + cc], fx, fy), c);
+  }
+  return pack_px<DT>(v);
+}
+
+// Sample blockIdx.y's descriptor {image byte offset, H0, W0, C, flip, y0, x0, ext}: slots 5..7 are 0 for a whole
+// image, ext == 1 for an unscaled crop at (y0, x0), ext == (sh << 32) | sw for a window of that extent.
+struct Desc {
+  long long off;
+  int H0, W0, C, flip, y0, x0;
+  long long ext;
+};
+
+__device__ __forceinline__ Desc load_desc(const long long* desc) {
+  const long long* d = desc + (size_t)blockIdx.y * 8;
+  return {d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], (int)d[5], (int)d[6], d[7]};
+}
+
 // img: uint8 [H0][W0][C] (C = 1, 3 or 4) -> out NHWC4 bf16 [Ho][Wo][4] (sample n of a batch)
 template <int DT>
 __global__ void __launch_bounds__(256) preprocess_image_kernel(const unsigned char* __restrict__ img, int H0, int W0,
                                                                int C, int flip, uint2* __restrict__ out, int Ho,
-                                                               int Wo, float m0, float m1, float m2, float is0,
-                                                               float is1, float is2) {
+                                                               int Wo) {
   const float sy = (float)H0 / (float)Ho, sx = (float)W0 / (float)Wo;
   const int total = Ho * Wo;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
@@ -40,16 +90,8 @@ __global__ void __launch_bounds__(256) preprocess_image_kernel(const unsigned ch
       x0 = W0 - 1 - x0;
       x1 = W0 - 1 - x1;
     }
-    float v[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int cc = (C == 1) ? 0 : c;
-      const float a = img[((size_t)y0 * W0 + x0) * C + cc], b = img[((size_t)y0 * W0 + x1) * C + cc];
-      const float d = img[((size_t)y1 * W0 + x0) * C + cc], e = img[((size_t)y1 * W0 + x1) * C + cc];
-      const float top = a + (b - a) * fx, bot = d + (e - d) * fx;
-      v[c] = (top + (bot - top) * fy) * (1.f / 255.f);
-    }
-    out[i] = make_uint2(pack2<DT>((v[0] - m0) * is0, (v[1] - m1) * is1), pack2<DT>((v[2] - m2) * is2, 0.f));
+    out[i] = resample_px<DT>(img + (size_t)y0 * W0 * C, img + (size_t)y1 * W0 * C, (size_t)x0 * C, (size_t)x1 * C, C,
+                             fx, fy);
   }
 }
 
@@ -65,64 +107,9 @@ __global__ void __launch_bounds__(256) preprocess_density_kernel(const float* __
     lin_tap(oy, sy, H0, y0, y1, fy);
     lin_tap(ox, sx, W0, x0, x1, fx);
     if (flip) { x0 = W0 - 1 - x0; x1 = W0 - 1 - x1; }
-    const float a = d[(size_t)y0 * W0 + x0], b = d[(size_t)y0 * W0 + x1];
-    const float c = d[(size_t)y1 * W0 + x0], e = d[(size_t)y1 * W0 + x1];
-    const float top = a + (b - a) * fx, bot = c + (e - c) * fx;
-    out[i] = (top + (bot - top) * fy) * mult;
-  }
-}
-
-// Whole batch in ONE launch: variable-size samples packed back to back in one uint8 image buffer and one
-// fp32 density buffer (one H2D copy each); desc[n] = {image byte offset, H0, W0, C, flip, density float
-// offset, 0, 0}.  blockIdx.y = sample, blockIdx.z = 0: image -> NHWC4 [Ho][Wo][4], 1: density -> [Ho/d][Wo/d].
-template <int DT>
-__global__ void __launch_bounds__(256) preprocess_batch_kernel(const unsigned char* __restrict__ imgs,
-                                                               const float* __restrict__ dens,
-                                                               const long long* __restrict__ desc,
-                                                               uint2* __restrict__ x4, float* __restrict__ gt, int Ho,
-                                                               int Wo, int ds, float mult) {
-  const long long* d = desc + (size_t)blockIdx.y * 8;
-  const int H0 = (int)d[1], W0 = (int)d[2], C = (int)d[3], flip = (int)d[4];
-  if (blockIdx.z == 0) {
-    const unsigned char* img = imgs + d[0];
-    uint2* out = x4 + (size_t)blockIdx.y * Ho * Wo;
-    const float sy = (float)H0 / (float)Ho, sx = (float)W0 / (float)Wo;
-    const float m[3] = {0.485f, 0.456f, 0.406f}, is[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < Ho * Wo; i += gridDim.x * 256) {
-      const int oy = i / Wo, ox = i % Wo;
-      int y0, y1, x0, x1;
-      float fy, fx;
-      lin_tap(oy, sy, H0, y0, y1, fy);
-      lin_tap(ox, sx, W0, x0, x1, fx);
-      if (flip) { x0 = W0 - 1 - x0; x1 = W0 - 1 - x1; }
-      float v[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int cc = (C == 1) ? 0 : c;
-        const float a = img[((size_t)y0 * W0 + x0) * C + cc], b = img[((size_t)y0 * W0 + x1) * C + cc];
-        const float e0 = img[((size_t)y1 * W0 + x0) * C + cc], e1 = img[((size_t)y1 * W0 + x1) * C + cc];
-        const float top = a + (b - a) * fx, bot = e0 + (e1 - e0) * fx;
-        v[c] = ((top + (bot - top) * fy) * (1.f / 255.f) - m[c]) * is[c];
-      }
-      out[i] = make_uint2(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], 0.f));
-    }
-  } else {
-    const float* dm = dens + d[5];
-    const int Hd = Ho / ds, Wd = Wo / ds;
-    float* out = gt + (size_t)blockIdx.y * Hd * Wd;
-    const float sy = (float)H0 / (float)Hd, sx = (float)W0 / (float)Wd;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < Hd * Wd; i += gridDim.x * 256) {
-      const int oy = i / Wd, ox = i % Wd;
-      int y0, y1, x0, x1;
-      float fy, fx;
-      lin_tap(oy, sy, H0, y0, y1, fy);
-      lin_tap(ox, sx, W0, x0, x1, fx);
-      if (flip) { x0 = W0 - 1 - x0; x1 = W0 - 1 - x1; }
-      const float a = dm[(size_t)y0 * W0 + x0], b = dm[(size_t)y0 * W0 + x1];
-      const float c = dm[(size_t)y1 * W0 + x0], e = dm[(size_t)y1 * W0 + x1];
-      const float top = a + (b - a) * fx, bot = c + (e - c) * fx;
-      out[i] = (top + (bot - top) * fy) * mult;
-    }
+    const float* ra = d + (size_t)y0 * W0;
+    const float* rb = d + (size_t)y1 * W0;
+    out[i] = blend4(ra[x0], ra[x1], rb[x0], rb[x1], fx, fy) * mult;
   }
 }
 
@@ -135,55 +122,52 @@ template <int DT>
 __global__ void __launch_bounds__(256) preprocess_crop_kernel(const unsigned char* __restrict__ imgs,
                                                               const long long* __restrict__ desc,
                                                               uint4* __restrict__ x4, int CH, int CW, int ds) {
-  const long long* d = desc + (size_t)blockIdx.y * 8;
-  const int H0 = (int)d[1], W0 = (int)d[2], C = (int)d[3], flip = (int)d[4], y0 = (int)d[5], x0 = (int)d[6];
-  const int vh = min(CH, H0 / ds * ds), vw = min(CW, W0 / ds * ds);
-  const unsigned char* img = imgs + d[0];
+  const Desc s = load_desc(desc);
+  const int vh = min(CH, s.H0 / ds * ds), vw = min(CW, s.W0 / ds * ds);
+  const unsigned char* img = imgs + s.off;
   const int half = CW / 2;
   uint4* out = x4 + (size_t)blockIdx.y * CH * half;
-  const float m[3] = {0.485f, 0.456f, 0.406f}, is[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
   for (int i = blockIdx.x * 256 + threadIdx.x; i < CH * half; i += gridDim.x * 256) {
     const int oy = i / half, ox = (i % half) * 2;
-    unsigned int w[4] = {0u, 0u, 0u, 0u};
+    uint2 w[2] = {make_uint2(0u, 0u), make_uint2(0u, 0u)};
     if (oy < vh) {
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         const int x = ox + p;
         if (x < vw) {
-          const int sx = x0 + (flip ? vw - 1 - x : x);
-          const unsigned char* px = img + ((size_t)(y0 + oy) * W0 + sx) * C;
+          const int sx = s.x0 + (s.flip ? vw - 1 - x : x);
+          const unsigned char* px = img + ((size_t)(s.y0 + oy) * s.W0 + sx) * s.C;
           float v[3];
 #pragma unroll
-          for (int c = 0; c < 3; ++c) v[c] = ((float)px[(C == 1) ? 0 : c] * (1.f / 255.f) - m[c]) * is[c];
-          w[2 * p] = pack2<DT>(v[0], v[1]);
-          w[2 * p + 1] = pack2<DT>(v[2], 0.f);
+          for (int c = 0; c < 3; ++c) v[c] = normalise((float)px[(s.C == 1) ? 0 : c], c);
+          w[p] = pack_px<DT>(v);
         }
       }
     }
-    out[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    out[i] = make_uint4(w[0].x, w[0].y, w[1].x, w[1].y);
   }
 }
 
-// Random-scale crop batch in ONE launch: desc[n] = {image byte offset, H0, W0, C, flip, y0, x0, (sh << 32) | sw}.
-// Output sample n = the window [y0, y0+sh) x [x0, x0+sw) of its image resampled to CH x CW by the cv2 INTER_LINEAR
-// rule (lin_tap relative to the window, taps clamped inside it; column taps mirrored within the window when
-// flipped), normalised in preprocess_batch_kernel's operation order.  No padding: the whole crop is valid.  It reads
-// only bytes of the window.  For sh == CH, sw == CW every fraction is exactly 0 and the blend returns the pixel
-// itself, so the output is bitwise preprocess_crop_kernel's.  A thread writes two adjacent NHWC4 pixels as one
-// 16-byte store (CW is even).
+// Resize batch and random-scale crop batch, ONE launch either way.  Output sample n = a window of its image resampled
+// to CH x CW by the cv2 INTER_LINEAR rule (lin_tap relative to the window, taps clamped inside it; column taps
+// mirrored within the window when flipped: the flip comes BEFORE the resize), normalised.  The window is the whole
+// image where slot 7 of the descriptor is 0 (an uncropped pack, can_preprocess_batch) and [y0, y0+sh) x [x0, x0+sw)
+// where it is (sh << 32) | sw (can_preprocess_crop_scaled); several descriptors may share one image.  No padding:
+// the whole sample is valid.  It reads only bytes of the window.  For sh == CH, sw == CW every fraction is exactly 0
+// and the blend returns the pixel itself, so the output is bitwise preprocess_crop_kernel's.  A thread writes two
+// adjacent NHWC4 pixels as one 16-byte store (CW is even).
 template <int DT>
-__global__ void __launch_bounds__(256) preprocess_crop_scaled_kernel(const unsigned char* __restrict__ imgs,
-                                                                     const long long* __restrict__ desc,
-                                                                     uint4* __restrict__ x4, int CH, int CW) {
-  const long long* d = desc + (size_t)blockIdx.y * 8;
-  const int W0 = (int)d[2], C = (int)d[3], flip = (int)d[4], y0 = (int)d[5], x0 = (int)d[6];
-  const int sh = (int)(d[7] >> 32), sw = (int)(d[7] & 0xffffffffll);
-  const unsigned char* win = imgs + d[0] + ((size_t)y0 * W0 + x0) * C;      // the window's first pixel
-  const size_t pitch = (size_t)W0 * C;
+__global__ void __launch_bounds__(256) preprocess_resample_kernel(const unsigned char* __restrict__ imgs,
+                                                                  const long long* __restrict__ desc,
+                                                                  uint4* __restrict__ x4, int CH, int CW) {
+  const Desc s = load_desc(desc);
+  const int sh = s.ext ? (int)(s.ext >> 32) : s.H0, sw = s.ext ? (int)(s.ext & 0xffffffffll) : s.W0;
+  const int y0 = s.ext ? s.y0 : 0, x0 = s.ext ? s.x0 : 0;
+  const unsigned char* win = imgs + s.off + ((size_t)y0 * s.W0 + x0) * s.C;      // the window's first pixel
+  const size_t pitch = (size_t)s.W0 * s.C;
   const float sy = (float)sh / (float)CH, sx = (float)sw / (float)CW;
   const int half = CW / 2;
   uint4* out = x4 + (size_t)blockIdx.y * CH * half;
-  const float m[3] = {0.485f, 0.456f, 0.406f}, is[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
   for (int i = blockIdx.x * 256 + threadIdx.x; i < CH * half; i += gridDim.x * 256) {
     const int oy = i / half, ox = (i % half) * 2;
     int ya, yb;
@@ -191,27 +175,16 @@ __global__ void __launch_bounds__(256) preprocess_crop_scaled_kernel(const unsig
     lin_tap(oy, sy, sh, ya, yb, fy);
     const unsigned char* ra = win + (size_t)ya * pitch;
     const unsigned char* rb = win + (size_t)yb * pitch;
-    unsigned int w[4];
+    uint2 w[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       int xa, xb;
       float fx;
       lin_tap(ox + p, sx, sw, xa, xb, fx);
-      if (flip) { xa = sw - 1 - xa; xb = sw - 1 - xb; }      // flip BEFORE the resize: mirror within the window
-      const size_t oa = (size_t)xa * C, ob = (size_t)xb * C;
-      float v[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int cc = (C == 1) ? 0 : c;
-        const float a = ra[oa + cc], b = ra[ob + cc];
-        const float e0 = rb[oa + cc], e1 = rb[ob + cc];
-        const float top = a + (b - a) * fx, bot = e0 + (e1 - e0) * fx;
-        v[c] = ((top + (bot - top) * fy) * (1.f / 255.f) - m[c]) * is[c];
-      }
-      w[2 * p] = pack2<DT>(v[0], v[1]);
-      w[2 * p + 1] = pack2<DT>(v[2], 0.f);
+      if (s.flip) { xa = sw - 1 - xa; xb = sw - 1 - xb; }
+      w[p] = resample_px<DT>(ra, rb, (size_t)xa * s.C, (size_t)xb * s.C, s.C, fx, fy);
     }
-    out[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    out[i] = make_uint4(w[0].x, w[0].y, w[1].x, w[1].y);
   }
 }
 
@@ -259,7 +232,6 @@ __global__ void __launch_bounds__(256) synth_image_kernel(const float* __restric
   const float* d = dens + (size_t)n * H * W;
   const float* nz = noise + (size_t)n * 3 * Hn * Wn;
   const float inv = 1.f / (dmax[n] + 1e-6f);
-  const float m[3] = {0.485f, 0.456f, 0.406f}, is[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
   for (int i = blockIdx.x * 256 + threadIdx.x; i < H * W; i += gridDim.x * 256) {
     const int oy = i / W, ox = i % W;
     int y0, y1, x0, x1;
@@ -271,27 +243,51 @@ __global__ void __launch_bounds__(256) synth_image_kernel(const float* __restric
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float* p = nz + (size_t)c * Hn * Wn;
-      const float top = p[y0 * Wn + x0] + (p[y0 * Wn + x1] - p[y0 * Wn + x0]) * fx;
-      const float bot = p[y1 * Wn + x0] + (p[y1 * Wn + x1] - p[y1 * Wn + x0]) * fx;
-      const float px = fminf(fmaxf(0.7f * (top + (bot - top) * fy) + blob, 0.f), 1.f);
-      v[c] = (px - m[c]) * is[c];
+      const float up = blend4(p[y0 * Wn + x0], p[y0 * Wn + x1], p[y1 * Wn + x0], p[y1 * Wn + x1], fx, fy);
+      v[c] = imagenet(fminf(fmaxf(0.7f * up + blob, 0.f), 1.f), c);
     }
-    x4[(size_t)n * H * W + i] = make_uint2(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], 0.f));
+    x4[(size_t)n * H * W + i] = pack_px<DT>(v);
   }
 }
 
 }  // namespace can
 
+namespace {
+
+// blocks of 256 threads for `work` items, capped: the kernels stride over what is left
+int capped_grid(long long work, int cap) {
+  const long long b = (work + 255) / 256;
+  return (int)(b < cap ? b : cap);
+}
+
+// the arguments of a crop launch, apart from the descriptors
+bool crop_args_ok(const void* imgs, const long long* desc, const long long* desc_host, int n, const void* x4, int CH,
+                  int CW, int ds) {
+  if (n <= 0 || n > 65535 || ds <= 0 || CH <= 0 || CW <= 0 || CH % ds || CW % ds || CW % 2) return false;
+  if ((long long)CH * CW > 0x7fffffff) return false;
+  return imgs != nullptr && desc != nullptr && desc_host != nullptr && x4 != nullptr && !((uintptr_t)x4 & 15);
+}
+
+// one host descriptor: a 1-, 3- or 4-channel image inside the img_bytes of packed images, and a window of extent
+// eh x ew at (y0, x0) inside that image
+bool crop_desc_ok(const long long* d, long long img_bytes, long long eh, long long ew) {
+  const long long off = d[0], H0 = d[1], W0 = d[2], C = d[3], flip = d[4], y0 = d[5], x0 = d[6];
+  if ((C != 1 && C != 3 && C != 4) || (flip != 0 && flip != 1)) return false;
+  if (H0 <= 0 || W0 <= 0 || H0 > 0x7fffffff || W0 > 0x7fffffff) return false;
+  if (off < 0 || off > img_bytes || H0 * W0 > (img_bytes - off) / C) return false;
+  return y0 >= 0 && x0 >= 0 && y0 <= H0 - eh && x0 <= W0 - ew;
+}
+
+}  // namespace
+
+// Images only: the ground truth of a pack arrives at 1/ds resolution already, so dens and gt must be null.
 extern "C" int can_preprocess_batch(const void* imgs, const float* dens, const long long* desc, int n, void* x4,
                                     float* gt, int Ho, int Wo, int ds, int dt, void* stream) {
   using namespace can;
-  if (n <= 0 || Ho % ds || Wo % ds) return -2;
-  int bx = (Ho * Wo + 255) / 256;
-  if (bx > 512) bx = 512;
-  // dens == nullptr: the ground truth arrived already at 1/ds resolution (images only)
-  CAN_LAUNCH_DT(dt, preprocess_batch_kernel, dim3(bx, n, (dens != nullptr && gt != nullptr) ? 2 : 1), dim3(256), 0,
-                (hipStream_t)stream,
-                (const unsigned char*)imgs, dens, desc, (uint2*)x4, gt, Ho, Wo, ds, (float)(ds * ds));
+  if (n <= 0 || Ho % ds || Wo % ds || Wo % 2 || ((uintptr_t)x4 & 15)) return -2;
+  if (dens != nullptr || gt != nullptr) return -2;
+  CAN_LAUNCH_DT(dt, preprocess_resample_kernel, dim3(capped_grid((long long)Ho * (Wo / 2), 512), n), dim3(256), 0,
+                (hipStream_t)stream, (const unsigned char*)imgs, desc, (uint4*)x4, Ho, Wo);
   return (int)hipGetLastError();
 }
 
@@ -301,49 +297,32 @@ extern "C" int can_preprocess_crop(const void* imgs, long long img_bytes, const 
                                    const long long* desc_host, int n, void* x4, int CH, int CW, int ds, int dt,
                                    void* stream) {
   using namespace can;
-  if (n <= 0 || n > 65535 || ds <= 0 || CH <= 0 || CW <= 0 || CH % ds || CW % ds || CW % 2) return -2;
-  if ((long long)CH * CW > 0x7fffffff) return -2;
-  if (imgs == nullptr || desc == nullptr || desc_host == nullptr || x4 == nullptr || ((uintptr_t)x4 & 15)) return -2;
+  if (!crop_args_ok(imgs, desc, desc_host, n, x4, CH, CW, ds)) return -2;
   for (int i = 0; i < n; ++i) {
     const long long* d = desc_host + (size_t)i * 8;
-    const long long off = d[0], H0 = d[1], W0 = d[2], C = d[3], flip = d[4], y0 = d[5], x0 = d[6];
-    if (d[7] != 1 || (C != 1 && C != 3 && C != 4) || (flip != 0 && flip != 1)) return -2;
-    if (H0 <= 0 || W0 <= 0 || H0 > 0x7fffffff || W0 > 0x7fffffff) return -2;
-    if (off < 0 || off > img_bytes || H0 * W0 > (img_bytes - off) / C) return -2;
-    const long long vh = H0 / ds * ds < CH ? H0 / ds * ds : CH, vw = W0 / ds * ds < CW ? W0 / ds * ds : CW;
-    if (y0 < 0 || x0 < 0 || y0 > H0 - vh || x0 > W0 - vw) return -2;
+    const long long vh = d[1] / ds * ds < CH ? d[1] / ds * ds : CH, vw = d[2] / ds * ds < CW ? d[2] / ds * ds : CW;
+    if (d[7] != 1 || !crop_desc_ok(d, img_bytes, vh, vw)) return -2;
   }
-  int bx = (CH * (CW / 2) + 255) / 256;
-  if (bx > 512) bx = 512;
-  CAN_LAUNCH_DT(dt, preprocess_crop_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream,
-                (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW, ds);
+  CAN_LAUNCH_DT(dt, preprocess_crop_kernel, dim3(capped_grid((long long)CH * (CW / 2), 512), n), dim3(256), 0,
+                (hipStream_t)stream, (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW, ds);
   return (int)hipGetLastError();
 }
 
-// can_preprocess_crop's checks, plus the window extents of slot 7: inside the image, and within a factor 4 of the crop
-// either way (the range of --crop-scale, with the rounding of the extents).
+// can_preprocess_crop's checks on the window extents of slot 7, which must also be inside the image and within a
+// factor 4 of the crop either way (the range of --crop-scale, with the rounding of the extents).
 extern "C" int can_preprocess_crop_scaled(const void* imgs, long long img_bytes, const long long* desc,
                                           const long long* desc_host, int n, void* x4, int CH, int CW, int ds, int dt,
                                           void* stream) {
   using namespace can;
-  if (n <= 0 || n > 65535 || ds <= 0 || CH <= 0 || CW <= 0 || CH % ds || CW % ds || CW % 2) return -2;
-  if ((long long)CH * CW > 0x7fffffff) return -2;
-  if (imgs == nullptr || desc == nullptr || desc_host == nullptr || x4 == nullptr || ((uintptr_t)x4 & 15)) return -2;
+  if (!crop_args_ok(imgs, desc, desc_host, n, x4, CH, CW, ds)) return -2;
   for (int i = 0; i < n; ++i) {
     const long long* d = desc_host + (size_t)i * 8;
-    const long long off = d[0], H0 = d[1], W0 = d[2], C = d[3], flip = d[4], y0 = d[5], x0 = d[6];
-    if (d[7] <= 1 || (C != 1 && C != 3 && C != 4) || (flip != 0 && flip != 1)) return -2;
     const long long sh = d[7] >> 32, sw = d[7] & 0xffffffffll;
-    if (H0 <= 0 || W0 <= 0 || H0 > 0x7fffffff || W0 > 0x7fffffff) return -2;
-    if (off < 0 || off > img_bytes || H0 * W0 > (img_bytes - off) / C) return -2;
-    if (sh < 1 || sw < 1 || sh > H0 || sw > W0) return -2;
-    if (y0 < 0 || x0 < 0 || y0 > H0 - sh || x0 > W0 - sw) return -2;
+    if (d[7] <= 1 || sh < 1 || sw < 1 || sh > d[1] || sw > d[2] || !crop_desc_ok(d, img_bytes, sh, sw)) return -2;
     if (sh > 4ll * CH || sw > 4ll * CW || CH > 4 * sh || CW > 4 * sw) return -2;
   }
-  int bx = (CH * (CW / 2) + 255) / 256;
-  if (bx > 512) bx = 512;
-  CAN_LAUNCH_DT(dt, preprocess_crop_scaled_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream,
-                (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW);
+  CAN_LAUNCH_DT(dt, preprocess_resample_kernel, dim3(capped_grid((long long)CH * (CW / 2), 512), n), dim3(256), 0,
+                (hipStream_t)stream, (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW);
   return (int)hipGetLastError();
 }
 
@@ -353,12 +332,10 @@ extern "C" int can_synth_render(const float* dens, const float* noise, float* dm
   if (n <= 0 || H % 16 || W % 16) return -2;
   hipStream_t s = (hipStream_t)stream;
   CAN_HIP_CHECK(hipMemsetAsync(dmax, 0, sizeof(float) * n, s));
-  int bx = (H / 8 * (W / 8) + 255) / 256;
-  if (bx > 256) bx = 256;
-  hipLaunchKernelGGL(synth_gt_kernel, dim3(bx, n), dim3(256), 0, s, dens, gt, dmax, H, W);
-  int bi = (H * W + 255) / 256;
-  if (bi > 1024) bi = 1024;
-  CAN_LAUNCH_DT(dt, synth_image_kernel, dim3(bi, n), dim3(256), 0, s, dens, noise, dmax, (uint2*)x4, H, W);
+  hipLaunchKernelGGL(synth_gt_kernel, dim3(capped_grid((long long)(H / 8) * (W / 8), 256), n), dim3(256), 0, s, dens,
+                     gt, dmax, H, W);
+  CAN_LAUNCH_DT(dt, synth_image_kernel, dim3(capped_grid((long long)H * W, 1024), n), dim3(256), 0, s, dens, noise,
+                dmax, (uint2*)x4, H, W);
   return (int)hipGetLastError();
 }
 
@@ -366,20 +343,15 @@ extern "C" int can_preprocess_image(const void* img, int H0, int W0, int C, int 
                                     void* stream) {
   using namespace can;
   if (C != 1 && C != 3 && C != 4) return -2;
-  const int total = Ho * Wo;
-  const int grid = (total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256;
-  CAN_LAUNCH_DT(dt, preprocess_image_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)img,
-                H0, W0, C, flip, (uint2*)out, Ho, Wo, 0.485f, 0.456f, 0.406f, 1.f / 0.229f, 1.f / 0.224f,
-                1.f / 0.225f);
+  CAN_LAUNCH_DT(dt, preprocess_image_kernel, dim3(capped_grid((long long)Ho * Wo, 4096)), dim3(256), 0,
+                (hipStream_t)stream, (const unsigned char*)img, H0, W0, C, flip, (uint2*)out, Ho, Wo);
   return (int)hipGetLastError();
 }
 
 extern "C" int can_preprocess_density(const float* d, int H0, int W0, int flip, float* out, int Ho, int Wo,
                                       float mult, void* stream) {
   using namespace can;
-  const int total = Ho * Wo;
-  const int grid = (total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256;
-  hipLaunchKernelGGL(preprocess_density_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d, H0, W0, flip, out,
-                     Ho, Wo, mult);
+  hipLaunchKernelGGL(preprocess_density_kernel, dim3(capped_grid((long long)Ho * Wo, 4096)), dim3(256), 0,
+                     (hipStream_t)stream, d, H0, W0, flip, out, Ho, Wo, mult);
   return (int)hipGetLastError();
 }

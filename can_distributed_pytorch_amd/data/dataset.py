@@ -56,11 +56,16 @@ def crop_window(h0: int, w0: int, ch: int, cw: int, downsample: int = 8):
     return min(ch, h0 // downsample * downsample), min(cw, w0 // downsample * downsample)
 
 
+def _draw_state(seed: int, epoch: int, index: int, k: int) -> int:
+    """The splitmix64 chain over (seed, epoch, index, k) that the draws of crop ``k`` hash once more per value."""
+    return _splitmix64(_splitmix64(_splitmix64(_splitmix64(seed & _M64) ^ (epoch & _M64)) ^ (index & _M64)) ^ (k & _M64))
+
+
 def crop_draw(seed: int, epoch: int, index: int, k: int, ny: int, nx: int):
     """Crop ``k`` of sample ``index`` in ``epoch``: (y0 uniform on [0, ny), x0 uniform on [0, nx), p=0.5 flip).
     Stateless like ``flip_draw`` (one splitmix64 chain over seed, epoch, index, k, then one hash per drawn value),
     so it depends neither on a worker's history nor on how many crops an image yields."""
-    s = _splitmix64(_splitmix64(_splitmix64(_splitmix64(seed & _M64) ^ (epoch & _M64)) ^ (index & _M64)) ^ (k & _M64))
+    s = _draw_state(seed, epoch, index, k)
     y0 = (_splitmix64(s ^ 1) * max(1, int(ny))) >> 64          # multiply-shift: bias < n / 2^64
     x0 = (_splitmix64(s ^ 2) * max(1, int(nx))) >> 64
     return int(y0), int(x0), bool(_splitmix64(s ^ 3) >> 63)
@@ -70,7 +75,7 @@ def scale_draw(seed: int, epoch: int, index: int, k: int, lo: float, hi: float) 
     """The scale of crop ``k`` of sample ``index`` in ``epoch``: log-uniform on [lo, hi], > 1 magnifies.  One more hash
     of ``crop_draw``'s chain state, so it is as stateless (no dependence on K, workers or resumes) and leaves the
     offset and flip draws what they are."""
-    s = _splitmix64(_splitmix64(_splitmix64(_splitmix64(seed & _M64) ^ (epoch & _M64)) ^ (index & _M64)) ^ (k & _M64))
+    s = _draw_state(seed, epoch, index, k)
     u = (_splitmix64(s ^ 4) >> 11) / 2 ** 53
     return float(min(hi, max(lo, lo * (hi / lo) ** u)))
 
@@ -92,6 +97,15 @@ def scaled_window(h0: int, w0: int, ch: int, cw: int, s: float):
     sh = min(h0, max(1, int(np.floor(ch / s_eff + 0.5))))
     sw = min(w0, max(1, int(np.floor(cw / s_eff + 0.5))))
     return sh, sw
+
+
+def _as_uint8(img: np.ndarray) -> np.ndarray:
+    """The decoded image as the writable, C-contiguous uint8 array the GPU path packs: float images are x255, every
+    other type is clipped to [0, 255]."""
+    if img.dtype != np.uint8:
+        img = np.clip(np.asarray(img, dtype=np.float64) * (255.0 if img.dtype.kind == "f" else 1.0),
+                      0, 255).astype(np.uint8)
+    return np.require(img, requirements=("C", "W"))
 
 
 def _pad_to(a: np.ndarray, h: int, w: int) -> np.ndarray:
@@ -238,69 +252,47 @@ class CrowdDataset(Dataset):
             # the GPU resizes / normalises the image; the ground truth is brought to its 1/d resolution here,
             # reading only the source rows the bilinear taps touch (memory-mapped: ~1/4 of a full-resolution
             # fp32 map), so a batch moves ~8x fewer host bytes than shipping full-resolution densities
-            if img.dtype != np.uint8:
-                img = np.clip(np.asarray(img, dtype=np.float64) * (255.0 if img.dtype.kind == "f" else 1.0),
-                              0, 255).astype(np.uint8)
             dmap = np.load(self.gt_path(name), mmap_mode="r")        # allow_pickle=False (default)
             gt = density_to_gt(dmap, img.shape[0], img.shape[1], self.gt_downsample, flip)
-            return torch.from_numpy(np.require(img, requirements=("C", "W"))), torch.from_numpy(gt), flip
+            return torch.from_numpy(_as_uint8(img)), torch.from_numpy(gt), flip
         dmap = np.load(self.gt_path(name))                       # allow_pickle=False (default)
         im, dm = prepare_pair(img, dmap, self.gt_downsample, flip)
         return torch.from_numpy(np.ascontiguousarray(im)), torch.from_numpy(np.ascontiguousarray(dm))
 
 
     def _crop_item(self, img: np.ndarray, name: str, epoch: int, index: int):
-        """K crops of one decoded image.  raw=False: ([K,3,ch,cw] f32, [K,1,ch/d,cw/d] f32), each prepare_pair of the
-        window's slices, zero-padded.  raw=True: (uint8 image, [K,1,ch/d,cw/d] f32, int64 [K,3] of (y0, x0, flip)):
-        the GPU cuts the windows (ops/preprocess.py), the ground truths are made here from the memory-mapped map."""
+        """K crops of one decoded image, crop k the window (y0, x0, wh, ww) placed by crop_draw: the (vh, vw) of
+        crop_window, zero-padded to the crop, or with crop_scale the scaled_window of its scale_draw, resampled to it.
+        raw=False: ([K,3,ch,cw] f32, [K,1,ch/d,cw/d] f32), each prepare_pair / prepare_pair_scaled of the window's
+        slices.  raw=True: (uint8 image, [K,1,ch/d,cw/d] f32, int64 windows [K,3] of (y0, x0, flip) or, scaled, [K,5]
+        of (y0, x0, flip, sh, sw)): the GPU cuts the windows (ops/preprocess.py), the ground truths are made here from
+        the memory-mapped map."""
         d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
         h0, w0 = img.shape[:2]
         dmap = np.load(self.gt_path(name), mmap_mode="r" if self.raw else None)      # allow_pickle=False (default)
         if tuple(dmap.shape) != (h0, w0):
             raise ValueError(f"{name}: density map {tuple(dmap.shape)} differs from its image {(h0, w0)}: a crop "
                              "takes the same window of both")
-        if self.crop_scale is not None:
-            return self._scaled_crop_item(img, dmap, epoch, index)
-        vh, vw = crop_window(h0, w0, ch, cw, d)
-        draws = [crop_draw(self.seed, epoch, index, k, h0 - vh + 1, w0 - vw + 1) for k in range(K)]
-        if self.raw:
-            if img.dtype != np.uint8:
-                img = np.clip(np.asarray(img, dtype=np.float64) * (255.0 if img.dtype.kind == "f" else 1.0),
-                              0, 255).astype(np.uint8)
-            gts = np.stack([_pad_to(density_to_gt(dmap[y0:y0 + vh, x0:x0 + vw], vh, vw, d, fl), ch // d, cw // d)
-                            for y0, x0, fl in draws])
-            wins = torch.tensor([[y0, x0, int(fl)] for y0, x0, fl in draws], dtype=torch.int64)
-            return torch.from_numpy(np.require(img, requirements=("C", "W"))), torch.from_numpy(gts), wins
-        ims, dms = [], []
-        for y0, x0, fl in draws:
-            im, dm = prepare_pair(img[y0:y0 + vh, x0:x0 + vw], dmap[y0:y0 + vh, x0:x0 + vw], d, fl)
-            ims.append(_pad_to(im, ch, cw))
-            dms.append(_pad_to(dm, ch // d, cw // d))
-        return torch.from_numpy(np.stack(ims)), torch.from_numpy(np.stack(dms))
-
-    def _scaled_crop_item(self, img: np.ndarray, dmap: np.ndarray, epoch: int, index: int):
-        """_crop_item with crop_scale: crop k resamples the window (y0, x0, sh, sw) = scaled_window of its scale_draw,
-        placed by crop_draw.  raw=False: the K prepare_pair_scaled pairs.  raw=True: (uint8 image, [K,1,ch/d,cw/d]
-        f32, int64 [K,5] of (y0, x0, flip, sh, sw)), the GPU resamples the windows (ops/preprocess.py)."""
-        d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
-        h0, w0 = img.shape[:2]
-        lo, hi = self.crop_scale
-        wins = []
+        scaled = self.crop_scale is not None
+        ims, gts, rows = [], [], []
         for k in range(K):
-            sh, sw = scaled_window(h0, w0, ch, cw, scale_draw(self.seed, epoch, index, k, lo, hi))
-            y0, x0, fl = crop_draw(self.seed, epoch, index, k, h0 - sh + 1, w0 - sw + 1)
-            wins.append((y0, x0, int(fl), sh, sw))
+            if scaled:
+                wh, ww = scaled_window(h0, w0, ch, cw, scale_draw(self.seed, epoch, index, k, *self.crop_scale))
+            else:
+                wh, ww = crop_window(h0, w0, ch, cw, d)
+            y0, x0, fl = crop_draw(self.seed, epoch, index, k, h0 - wh + 1, w0 - ww + 1)
+            im, dm = img[y0:y0 + wh, x0:x0 + ww], dmap[y0:y0 + wh, x0:x0 + ww]
+            rows.append([y0, x0, int(fl)] + ([wh, ww] if scaled else []))
+            if self.raw:
+                gt = density_to_gt_scaled(dm, ch, cw, d, fl) if scaled else density_to_gt(dm, wh, ww, d, fl)
+            else:
+                im, gt = prepare_pair_scaled(im, dm, ch, cw, d, fl) if scaled else prepare_pair(im, dm, d, fl)
+                ims.append(_pad_to(im, ch, cw))
+            gts.append(_pad_to(gt, ch // d, cw // d))
+        gts = torch.from_numpy(np.stack(gts))
         if self.raw:
-            if img.dtype != np.uint8:
-                img = np.clip(np.asarray(img, dtype=np.float64) * (255.0 if img.dtype.kind == "f" else 1.0),
-                              0, 255).astype(np.uint8)
-            gts = np.stack([density_to_gt_scaled(dmap[y0:y0 + sh, x0:x0 + sw], ch, cw, d, bool(fl))
-                            for y0, x0, fl, sh, sw in wins])
-            return (torch.from_numpy(np.require(img, requirements=("C", "W"))), torch.from_numpy(gts),
-                    torch.tensor(wins, dtype=torch.int64))
-        pairs = [prepare_pair_scaled(img[y0:y0 + sh, x0:x0 + sw], dmap[y0:y0 + sh, x0:x0 + sw], ch, cw, d, bool(fl))
-                 for y0, x0, fl, sh, sw in wins]
-        return (torch.from_numpy(np.stack([p[0] for p in pairs])), torch.from_numpy(np.stack([p[1] for p in pairs])))
+            return torch.from_numpy(_as_uint8(img)), gts, torch.tensor(rows, dtype=torch.int64)
+        return torch.from_numpy(np.stack(ims)), gts
 
 
 class SyntheticCrowdDataset(Dataset):

@@ -12,7 +12,8 @@ ONE kernel launch turns the batch into network inputs (``preprocess_packed``).
 ``PackedCollate(crop=(ch, cw))`` packs random-crop batches: every image once,
 one descriptor per crop, cut on the GPU by one launch of the crop kernel;
 with ``crop_scale=True`` every descriptor carries its window's extent and the
-scaled crop kernel resamples it to the crop.
+resize launch's kernel resamples it to the crop.  A pack of any kind goes
+through one collate loop, ``_unpack`` and ``_launch``.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ from typing import List, Sequence, Tuple
 import torch
 
 from . import _ext
+from .conv import dt_code
 
 
 def preprocess_batch(images: Sequence[torch.Tensor], densities: Sequence[torch.Tensor], flips: Sequence[bool],
@@ -34,7 +36,6 @@ def preprocess_batch(images: Sequence[torch.Tensor], densities: Sequence[torch.T
         raise ValueError("images, densities and flips must have the same non-zero length")
     h0, w0 = images[0].shape[:2]
     ho, wo = (h0 // downsample) * downsample, (w0 // downsample) * downsample
-    from .conv import dt_code
     dt = dt_code(dtype)
     x4 = torch.empty(n, ho, wo, 4, dtype=dtype, device=dev)
     gt = torch.empty(n, 1, ho // downsample, wo // downsample, dtype=torch.float32, device=dev)
@@ -57,14 +58,6 @@ def preprocess_batch(images: Sequence[torch.Tensor], densities: Sequence[torch.T
     return x4, gt
 
 
-class RawCollate:
-    """collate_fn for CrowdDataset(raw=True): keeps samples as lists (variable sizes allowed until preprocessing)."""
-
-    def __call__(self, batch: List):
-        imgs, dens, flips = zip(*batch)
-        return list(imgs), list(dens), list(flips)
-
-
 class PackedCollate:
     """collate_fn for CrowdDataset(raw=True) that packs a batch for ONE H2D copy and ONE launch: returns
     (buf uint8, (n, Ho, Wo, gt_offset, desc_offset)) where buf holds the images back to back (bytes
@@ -72,8 +65,14 @@ class PackedCollate:
     desc_offset (16-byte aligned), desc[i] = (image byte offset, H0, W0, C, flip, 0, 0, 0).  The raw dataset already
     brought each ground truth to 1/d resolution (flip and x d^2 included), so only the images are resized on the
     GPU.  Runs in the loader workers; pin_memory=True pins the buffer.  (Three separate pinned copies per batch were
-    ~0.23 ms of host time per step at batch 1: profiles/r5/host/.)  crop=(ch, cw): the random-crop form for
-    CrowdDataset(raw=True, crop=...) items, see ``_call_crop``; crop_scale=True: its items carry scaled windows."""
+    ~0.23 ms of host time per step at batch 1: profiles/r5/host/.)
+
+    crop=(ch, cw): the random-crop form, for CrowdDataset(raw=True, crop=...) items (uint8 image, gts
+    [K,1,ch/d,cw/d], windows [K,3] of (y0, x0, flip)): every image's bytes ONCE, the [B*K,1,ch/d,cw/d] ground truth
+    and one descriptor per output sample, desc = (image byte offset, H0, W0, C, flip, y0, x0, 1) -- the K crops of an
+    image share its offset.  The meta tuple gains a sixth field, the number of images, which marks the pack as cropped.
+    crop_scale=True: the windows are [K,5] of (y0, x0, flip, sh, sw), slot 7 of a descriptor is (sh << 32) | sw (never
+    the unscaled 1) and the meta tuple gains a seventh field, 1, which marks the pack as scaled."""
 
     def __init__(self, downsample: int = 8, crop=None, crop_scale=False):
         self.ds = downsample
@@ -84,33 +83,23 @@ class PackedCollate:
         if self.crop is not None and (min(self.crop) <= 0 or self.crop[0] % downsample or self.crop[1] % downsample):
             raise ValueError(f"crop {self.crop} must be a positive multiple of the downsample {downsample}")
 
-    def _call_crop(self, batch: List):
-        """CrowdDataset(raw=True, crop=...) items (uint8 image, gts [K,1,ch/d,cw/d], windows [K,3] of (y0, x0, flip)):
-        every image's bytes ONCE, the [B*K,1,ch/d,cw/d] ground truth and one descriptor per output sample,
-        desc = (image byte offset, H0, W0, C, flip, y0, x0, 1) -- the K crops of an image share its offset.  The
-        meta tuple gains a sixth field, the number of images, which marks the pack as cropped.
-        crop_scale: the windows are [K,5] of (y0, x0, flip, sh, sw), slot 7 of a descriptor is (sh << 32) | sw (never
-        the unscaled 1) and the meta tuple gains a seventh field, 1, which marks the pack as scaled."""
-        ch, cw = self.crop
+    def _windows(self, im, g, third, ho, wo):
+        """The (flip, y0, x0, slot 7) of every output sample of one item, checked against the pack's kind."""
+        d = self.ds
+        if self.crop is None:
+            if (im.shape[0] // d * d, im.shape[1] // d * d) != (ho, wo):
+                raise ValueError("all samples of a batch must resize to the same shape")
+            if tuple(g.shape) != (1, ho // d, wo // d):
+                raise ValueError("raw samples must carry the 1/d ground truth [1, H/d, W/d]")
+            return [(int(bool(third)), 0, 0, 0)]
         nw = 5 if self.crop_scale else 3
-        imgs, gts, wins = zip(*batch)
-        rows, ioff = [], 0
-        for im, g, wn in zip(imgs, gts, wins):
-            hh, ww = im.shape[:2]
-            c = 1 if im.dim() == 2 else im.shape[2]
-            if g.dim() != 4 or tuple(g.shape[1:]) != (1, ch // self.ds, cw // self.ds) or \
-                    tuple(wn.shape) != (g.shape[0], nw):
-                raise ValueError(f"cropped raw samples must carry ground truths [K, 1, ch/d, cw/d] and windows [K, {nw}]")
-            if self.crop_scale:
-                if int(wn[:, 3:].min()) < 1 or int(wn[:, 3:].max()) > 0x7fffffff:
-                    raise ValueError("scaled windows must have extents 1 <= sh, sw < 2^31")
-                rows += [[ioff, hh, ww, c, fl, y0, x0, (sh << 32) | sw] for y0, x0, fl, sh, sw in wn.tolist()]
-            else:
-                rows += [[ioff, hh, ww, c, fl, y0, x0, 1] for y0, x0, fl in wn.tolist()]
-            ioff += hh * ww * c
-        desc = torch.tensor(rows, dtype=torch.int64)
-        buf, goff, doff = self._fill(imgs, ioff, torch.cat(gts).float().contiguous(), desc)
-        return buf, (desc.shape[0], ch, cw, goff, doff, len(imgs)) + ((1,) if self.crop_scale else ())
+        if g.dim() != 4 or tuple(g.shape[1:]) != (1, ho // d, wo // d) or tuple(third.shape) != (g.shape[0], nw):
+            raise ValueError(f"cropped raw samples must carry ground truths [K, 1, ch/d, cw/d] and windows [K, {nw}]")
+        if not self.crop_scale:
+            return [(fl, y0, x0, 1) for y0, x0, fl in third.tolist()]
+        if int(third[:, 3:].min()) < 1 or int(third[:, 3:].max()) > 0x7fffffff:
+            raise ValueError("scaled windows must have extents 1 <= sh, sw < 2^31")
+        return [(fl, y0, x0, (sh << 32) | sw) for y0, x0, fl, sh, sw in third.tolist()]
 
     @staticmethod
     def _fill(imgs, ioff, gt, desc):
@@ -128,36 +117,54 @@ class PackedCollate:
         return buf, goff, doff
 
     def __call__(self, batch: List):
-        if self.crop is not None:
-            return self._call_crop(batch)
-        imgs, gts, flips = zip(*batch)
-        h0, w0 = imgs[0].shape[:2]
-        ho, wo = (h0 // self.ds) * self.ds, (w0 // self.ds) * self.ds
-        desc = torch.zeros(len(imgs), 8, dtype=torch.int64)
-        ioff = 0
-        for i, (im, g, fl) in enumerate(zip(imgs, gts, flips)):
+        imgs, gts, thirds = zip(*batch)            # the third field: a flip (uncropped) or the [K, 3 / 5] windows
+        if self.crop is None:
+            ho, wo = (imgs[0].shape[0] // self.ds) * self.ds, (imgs[0].shape[1] // self.ds) * self.ds
+        else:
+            ho, wo = self.crop
+        rows, ioff = [], 0
+        for im, g, third in zip(imgs, gts, thirds):
             hh, ww = im.shape[:2]
-            if (hh // self.ds * self.ds, ww // self.ds * self.ds) != (ho, wo):
-                raise ValueError("all samples of a batch must resize to the same shape")
-            if tuple(g.shape) != (1, ho // self.ds, wo // self.ds):
-                raise ValueError("raw samples must carry the 1/d ground truth [1, H/d, W/d]")
-            ch = 1 if im.dim() == 2 else im.shape[2]
-            desc[i] = torch.tensor([ioff, hh, ww, ch, int(bool(fl)), 0, 0, 0])
-            ioff += hh * ww * ch
-        buf, goff, doff = self._fill(imgs, ioff, torch.stack(gts).float().contiguous(), desc)
-        return buf, (len(imgs), ho, wo, goff, doff)
+            c = 1 if im.dim() == 2 else im.shape[2]
+            rows += [[ioff, hh, ww, c, *w] for w in self._windows(im, g, third, ho, wo)]
+            ioff += hh * ww * c
+        desc = torch.tensor(rows, dtype=torch.int64)
+        gt = (torch.stack(gts) if self.crop is None else torch.cat(gts)).float().contiguous()
+        buf, goff, doff = self._fill(imgs, ioff, gt, desc)
+        kind = () if self.crop is None else (len(imgs), 1) if self.crop_scale else (len(imgs),)
+        return buf, (len(rows), ho, wo, goff, doff) + kind
+
+
+KINDS = ("batch", "crop", "crop_scaled")         # a pack's kind: the C.preprocess_<kind> entry that takes it
 
 
 def _unpack(packed):
-    """(buf, (n, Ho, Wo, gt_offset, desc_offset), cropped, scaled) of a PackedCollate output; a cropped pack's meta
-    tuple carries a sixth field (its number of images) and n counts output samples, one descriptor each; a scaled
-    pack's carries a seventh, 1."""
+    """(buf, (n, Ho, Wo, gt_offset, desc_offset), kind) of a PackedCollate output, kind one of KINDS: a cropped
+    pack's meta tuple carries a sixth field (its number of images) and n counts output samples, one descriptor each;
+    a scaled pack's carries a seventh, 1."""
     buf, meta = packed
     n, ho, wo, goff, doff = meta[:5]
-    if len(meta) not in (5, 6, 7) or (len(meta) == 7 and meta[6] != 1) or buf.dtype != torch.uint8 or buf.dim() != 1 or goff % 16 or doff % 16 or \
-            buf.numel() != doff + 64 * n:
+    meta_ok = len(meta) in (5, 6) or (len(meta) == 7 and meta[6] == 1)
+    buf_ok = buf.dtype == torch.uint8 and buf.dim() == 1 and buf.numel() == doff + 64 * n
+    if not (meta_ok and buf_ok) or goff % 16 or doff % 16:
         raise ValueError("packed batch: one uint8 buffer (images | fp32 ground truth | int64 descriptors)")
-    return buf, (n, ho, wo, goff, doff), len(meta) == 6, len(meta) == 7
+    return buf, (n, ho, wo, goff, doff), KINDS[len(meta) - 5]
+
+
+def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device):
+    """The one launch of a pack of any kind: d, the device copy of buf -> (x4, gt), gt a view of d.  The crop entries
+    check the host descriptors (in buf) before they launch."""
+    hd, wd = ho // downsample, wo // downsample
+    gt = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
+    desc = d[doff:].view(torch.int64).view(n, 8)
+    x4 = torch.empty(n, ho, wo, 4, dtype=dtype, device=device)
+    tail = (ho, wo, downsample, dt_code(dtype), _ext.stream_ptr(device))
+    if kind == "batch":
+        C.preprocess_batch(d.data_ptr(), 0, desc.data_ptr(), n, x4.data_ptr(), 0, *tail)
+    else:
+        getattr(C, "preprocess_" + kind)(d.data_ptr(), goff, desc.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(),
+                                         *tail)
+    return x4, gt
 
 
 def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = torch.bfloat16,
@@ -167,9 +174,8 @@ def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = 
     compute stream then waits for it): a pinned copy queued behind the previous step's kernels on the compute stream
     held the host ~0.6 ms per step at batch 1 (profiles/r5/host/), one on an idle copy stream does not."""
     C = _ext.require()
-    buf, (n, ho, wo, goff, doff), cropped, scaled = _unpack(packed)
+    buf, dims, kind = _unpack(packed)
     dev = torch.device(device)
-    from .conv import dt_code
     if copy_stream is not None:
         cur = torch.cuda.current_stream(dev)
         with torch.cuda.stream(copy_stream):
@@ -178,21 +184,7 @@ def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = 
         d.record_stream(cur)              # allocated on the copy stream, consumed on the compute stream
     else:
         d = buf.to(dev, non_blocking=True)
-    ib = d
-    hd, wd = ho // downsample, wo // downsample
-    gtd = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
-    ds = d[doff:].view(torch.int64).view(n, 8)
-    x4 = torch.empty(n, ho, wo, 4, dtype=dtype, device=dev)
-    if scaled:
-        C.preprocess_crop_scaled(ib.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), ho, wo,
-                                 downsample, dt_code(dtype), _ext.stream_ptr(dev))
-    elif cropped:
-        C.preprocess_crop(ib.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), ho, wo,
-                          downsample, dt_code(dtype), _ext.stream_ptr(dev))
-    else:
-        C.preprocess_batch(ib.data_ptr(), 0, ds.data_ptr(), n, x4.data_ptr(), 0, ho, wo, downsample, dt_code(dtype),
-                           _ext.stream_ptr(dev))
-    return x4, gtd
+    return _launch(C, kind, buf, d, *dims, downsample, dtype, dev)
 
 
 class AheadPrep:
@@ -212,29 +204,15 @@ class AheadPrep:
         self.copy = torch.cuda.Stream(self.device)
 
     def issue(self, packed):
-        from .conv import dt_code
         C = _ext.require()
-        buf, (n, ho, wo, goff, doff), cropped, scaled = _unpack(packed)
+        buf, dims, kind = _unpack(packed)
         # the copy stream must not overwrite memory the compute stream's queued kernels may still read: wait for
         # what the compute stream has queued so far is NOT needed (fresh blocks of the copy stream's own pool), and
         # the hand-off below keeps the blocks out of that pool until the compute stream is done with them
         with torch.cuda.stream(self.copy):
             d = buf.to(self.device, non_blocking=True)
-            hd, wd = ho // self.ds, wo // self.ds
-            gt = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
-            ds = d[doff:].view(torch.int64).view(n, 8)
-            x4 = torch.empty(n, ho, wo, 4, dtype=self.dtype, device=self.device)
             with _ext.launch_on(self.copy.cuda_stream):
-                if scaled:
-                    C.preprocess_crop_scaled(d.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n,
-                                             x4.data_ptr(), ho, wo, self.ds, dt_code(self.dtype),
-                                             _ext.stream_ptr(self.device))
-                elif cropped:
-                    C.preprocess_crop(d.data_ptr(), goff, ds.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), ho,
-                                      wo, self.ds, dt_code(self.dtype), _ext.stream_ptr(self.device))
-                else:
-                    C.preprocess_batch(d.data_ptr(), 0, ds.data_ptr(), n, x4.data_ptr(), 0, ho, wo, self.ds,
-                                       dt_code(self.dtype), _ext.stream_ptr(self.device))
+                x4, gt = _launch(C, kind, buf, d, *dims, self.ds, self.dtype, self.device)
             ev = torch.cuda.Event()
             ev.record(self.copy)
         return x4, gt, d, ev

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """GPU time of the crop launch (csrc/preprocess.hip preprocess_crop_kernel) beside the resize launch
-(preprocess_batch_kernel) at the same output size: batch x HxW NHWC4 bf16 from packed uint8 RGB images already on
+(preprocess_resample_kernel) at the same output size: batch x HxW NHWC4 bf16 from packed uint8 RGB images already on
 the device.  Arms: resize of HxW sources (scale 1: four taps per pixel), crop of the same HxW sources (the window is
 the image) and crop of 2H x 2W sources at random offsets with flips.  hipEvents around ITERS back-to-back launches,
 best and median of REPS; one JSON line per arm.

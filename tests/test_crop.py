@@ -162,7 +162,7 @@ def test_packed_collate_crop_stores_each_image_once(crop_set):
     n, ho, wo, goff, doff = meta[:5]
     assert (n, ho, wo) == (6, 32, 48) and len(meta) == 6 and meta[5] == 2
     assert buf.dtype == torch.uint8 and goff % 16 == 0 and doff % 16 == 0 and buf.numel() == doff + 64 * n
-    assert _unpack(packed)[2] is True
+    assert _unpack(packed)[2] == "crop"
     nb0, nb1 = 77 * 101 * 3, 50 * 70
     assert goff == -(-(nb0 + nb1) // 16) * 16                 # both images once, nothing else ahead of the gt
     assert np.array_equal(buf[:nb0].numpy(), imgs[0].reshape(-1))
@@ -192,7 +192,7 @@ def test_packed_collate_without_crop_is_unchanged():
     goff = -(-(nb0 + nb1) // 16) * 16
     doff = -(-(goff + 4 * 2 * 9 * 12) // 16) * 16
     assert meta == (2, 72, 96, goff, doff) and buf.numel() == doff + 128
-    assert _unpack(packed)[2] is False
+    assert _unpack(packed)[2] == "batch"
     assert torch.equal(buf[:nb0 + nb1], torch.cat([s[0].reshape(-1) for s in samples]))
     assert torch.equal(buf[goff:goff + 4 * 216].view(torch.float32), torch.stack([s[1] for s in samples]).reshape(-1))
     assert buf[doff:].view(torch.int64).view(2, 8).tolist() == [[0, 77, 101, 3, 0, 0, 0, 0], [nb0, 79, 103, 1, 1, 0, 0, 0]]

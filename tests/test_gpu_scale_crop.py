@@ -228,8 +228,102 @@ def test_unscaled_packs_take_their_unchanged_launches():
     assert torch.equal(x4, ref) and torch.equal(a4, ref) and torch.equal(ag, gt)
 
 
+# ---------------------------------------------------------------- the launches against one another
+def _uncropped_pack(shapes, seed):
+    """An uncropped pack of random images of the given (H, W, C), flips alternating, zero ground truths."""
+    from can_distributed_pytorch_amd.ops.preprocess import PackedCollate
+    rng = np.random.default_rng(seed)
+    h, w = shapes[0][0] // D * D, shapes[0][1] // D * D
+    gt = torch.zeros(1, h // D, w // D)
+    return PackedCollate()([(torch.from_numpy(rng.integers(0, 256, (h0, w0, c) if c > 1 else (h0, w0), dtype=np.uint8)),
+                             gt, bool(i % 2)) for i, (h0, w0, c) in enumerate(shapes)])
+
+
+def _resize_launch(C, d, n, doff, ho, wo, dtype):
+    from can_distributed_pytorch_amd.ops import _ext
+    from can_distributed_pytorch_amd.ops.conv import dt_code
+    out = torch.empty(n, ho, wo, 4, dtype=dtype, device="cuda")
+    C.preprocess_batch(d.data_ptr(), 0, d[doff:].view(torch.int64).data_ptr(), n, out.data_ptr(), 0, ho, wo, D,
+                       dt_code(dtype), _ext.stream_ptr(torch.device("cuda")))
+    return out
+
+
+# the second case: 128 x 64 = 4096 pixel pairs, so a sample spans more than one block of either launch
+@pytest.mark.parametrize("shapes", [[(77, 101, 3), (72, 96, 3), (79, 103, 1), (72, 100, 4)], [(131, 71, 3)]],
+                         ids=["to72x96", "to128x64"])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_resize_launch_equals_scaled_launch_on_whole_image_windows(shapes, dtype):
+    """C.preprocess_batch on an uncropped pack == C.preprocess_crop_scaled on the same bytes with every window set
+    to its whole image, bit for bit: what lets one resample kernel serve both entries."""
+    from can_distributed_pytorch_amd.ops import _ext
+    from can_distributed_pytorch_amd.ops.conv import dt_code
+    C = _ext.require()
+    buf, (n, ho, wo, goff, doff) = _uncropped_pack(shapes, seed=12)
+    d = buf.cuda()
+    a4 = _resize_launch(C, d, n, doff, ho, wo, dtype)
+    whole = buf.clone()
+    rows = whole[doff:].view(torch.int64).view(n, 8)
+    assert rows[:, 4].tolist() == [i % 2 for i in range(n)] and not rows[:, 5:].any()
+    rows[:, 7] = (rows[:, 1] << 32) | rows[:, 2]
+    dw = whole.cuda()
+    b4 = torch.empty_like(a4)
+    C.preprocess_crop_scaled(dw.data_ptr(), goff, dw[doff:].view(torch.int64).data_ptr(), whole.data_ptr() + doff, n,
+                             b4.data_ptr(), ho, wo, D, dt_code(dtype), _ext.stream_ptr(torch.device("cuda")))
+    torch.cuda.synchronize()
+    assert (ho, wo) == ((72, 96) if n == 4 else (128, 64))
+    assert torch.equal(a4.view(torch.int16), b4.view(torch.int16))
+    assert bool((a4[..., :3].float().abs() > 0).any())
+
+
+@pytest.mark.parametrize("shape", [(77, 101, 3), (50, 70, 1)])
+@pytest.mark.parametrize("flip", [False, True])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_per_sample_form_equals_the_batch_launch_bit_for_bit(shape, flip, dtype):
+    """preprocess_batch (C.preprocess_image + C.preprocess_density per sample) against the batch launch on the same
+    single image, bit for bit.  The batch launch resizes images only: its density half had no caller, equalled
+    C.preprocess_density bit for bit when it was deleted (profiles/r14), and C.preprocess_density stays held to the
+    CPU transform by tests/test_gpu_components.py."""
+    from can_distributed_pytorch_amd.ops import _ext
+    from can_distributed_pytorch_amd.ops.preprocess import PackedCollate, preprocess_batch
+    C = _ext.require()
+    h0, w0, c = shape
+    rng = np.random.default_rng(13)
+    img = torch.from_numpy(rng.integers(0, 256, (h0, w0, c) if c > 1 else (h0, w0), dtype=np.uint8))
+    dm = torch.from_numpy(rng.random((h0, w0)).astype(np.float32))
+    buf, (n, ho, wo, goff, doff) = PackedCollate()([(img, torch.zeros(1, h0 // D, w0 // D), flip)])
+    a4 = _resize_launch(C, buf.cuda(), n, doff, ho, wo, dtype)
+    x4, gt = preprocess_batch([img], [dm], [flip], "cuda", dtype=dtype)
+    torch.cuda.synchronize()
+    assert x4.dtype == dtype and torch.equal(a4.view(torch.int16), x4.view(torch.int16))
+    assert bool((x4[..., :3].float().abs() > 0).any())
+    assert tuple(gt.shape) == (1, 1, h0 // D, w0 // D) and bool(torch.isfinite(gt).all())
+
+
+def test_resize_launch_refuses_densities_before_any_launch():
+    """C.preprocess_batch resizes images only: a non-null density or ground-truth pointer is refused."""
+    from can_distributed_pytorch_amd.ops import _ext
+    from can_distributed_pytorch_amd.ops.conv import dt_code
+    C = _ext.require()
+    buf, (n, ho, wo, goff, doff) = _uncropped_pack([(77, 101, 3), (72, 96, 3)], seed=14)
+    d = buf.cuda()
+    st = _ext.stream_ptr(torch.device("cuda"))
+    canary = torch.full((n, ho, wo, 4), 7.0, dtype=torch.bfloat16, device="cuda")
+    dens = torch.zeros(77 * 101 + 72 * 96, device="cuda")
+    gt = torch.full((n, 1, ho // D, wo // D), 7.0, device="cuda")
+    for dp, gp in ((dens.data_ptr(), gt.data_ptr()), (dens.data_ptr(), 0), (0, gt.data_ptr())):
+        with pytest.raises(RuntimeError, match="preprocess_batch"):
+            C.preprocess_batch(d.data_ptr(), dp, d[doff:].view(torch.int64).data_ptr(), n, canary.data_ptr(), gp, ho,
+                               wo, D, dt_code(torch.bfloat16), st)
+    torch.cuda.synchronize()
+    assert bool((canary == 7.0).all()) and bool((gt == 7.0).all())          # nothing was launched
+    C.preprocess_batch(d.data_ptr(), 0, d[doff:].view(torch.int64).data_ptr(), n, canary.data_ptr(), 0, ho, wo, D,
+                       dt_code(torch.bfloat16), st)
+    torch.cuda.synchronize()
+    assert not bool((canary == 7.0).any())
+
+
 # ---------------------------------------------------------------- train.py end to end
-SIZES = [(96, 128), (104, 120), (80, 160), (64, 72), (96, 128), (104, 120)]        # 64 x 72 < the 64 x 96 crop
+SIZES =[(96, 128), (104, 120), (80, 160), (64, 72), (96, 128), (104, 120)]        # 64 x 72 < the 64 x 96 crop
 
 
 @pytest.fixture(scope="module")

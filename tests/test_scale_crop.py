@@ -57,6 +57,17 @@ def test_crop_draw_is_what_it_was():
     assert crop_draw(0, 0, 0, 0, 46, 54) == (29, 1, True)
 
 
+def test_both_draws_are_what_they_were():
+    """Literals computed with the code before the two draws shared their chain state."""
+    tuples = [(3, 2, 7, 1), (11, 0, 5, 2), (2 ** 40 + 5, 123, 999, 17), (0, 0, 0, 0)]
+    assert [crop_draw(*t, 1000, 777) for t in tuples] == [(436, 246, True), (473, 592, True), (697, 688, False),
+                                                          (647, 15, True)]
+    assert [scale_draw(*t, 0.5, 2.0) for t in tuples] == [1.485580203883466, 0.82089857378068, 1.2501406608339898,
+                                                          1.4574052934975077]
+    assert [scale_draw(*t, 0.75, 1.33) for t in tuples] == [1.1762222783373204, 0.9205304144750743, 1.09527443808346,
+                                                            1.1669521902254036]
+
+
 @pytest.mark.parametrize("h0,w0", SHAPES)
 def test_window_fits_its_image(h0, w0):
     ch, cw = CROP
@@ -303,7 +314,7 @@ def test_packed_collate_scaled_layout(scale_set):
     buf, meta = packed
     n, ho, wo, goff, doff, n_img, scaled = meta
     assert (n, ho, wo, n_img, scaled) == (3 * K, ch, cw, 3, 1) and len(meta) == 7
-    assert _unpack(packed)[1:] == ((n, ho, wo, goff, doff), False, True)
+    assert _unpack(packed)[1:] == ((n, ho, wo, goff, doff), "crop_scaled")
     sizes = [imgs[i].size for i in (3, 0, 2)]
     assert goff == -(-sum(sizes) // 16) * 16 and doff == -(-(goff + 4 * n * (ch // D) * (cw // D)) // 16) * 16
     assert buf.numel() == doff + 64 * n
@@ -330,8 +341,53 @@ def test_packed_collate_scaled_layout(scale_set):
         _unpack((buf, meta[:6] + (0,)))
     # an unscaled cropped pack is what it was: six meta fields, slot 7 == 1
     pb, pm = PackedCollate(crop=CROP)([plain[2]])
-    assert len(pm) == 6 and _unpack((pb, pm))[2:] == (True, False)
+    assert len(pm) == 6 and _unpack((pb, pm))[2] == "crop"
     assert pb[pm[4]:].view(torch.int64).view(K, 8)[:, 7].tolist() == [1] * K
+
+
+def _assemble(imgs, gt, rows):
+    """The documented layout, built independently: images | 16-byte-aligned fp32 ground truth | 16-byte-aligned int64
+    descriptors.  Returns (bytes, defined): the alignment gaps carry no defined bytes."""
+    ib = np.concatenate([np.asarray(im).reshape(-1) for im in imgs])
+    goff = (ib.size + 15) // 16 * 16
+    gb = np.ascontiguousarray(gt, dtype="<f4").reshape(-1).view(np.uint8)
+    doff = (goff + gb.size + 15) // 16 * 16
+    db = np.array(rows, dtype="<i8").reshape(-1).view(np.uint8)
+    buf, defined = np.zeros(doff + db.size, np.uint8), np.zeros(doff + db.size, bool)
+    for off, part in ((0, ib), (goff, gb), (doff, db)):
+        buf[off:off + part.size], defined[off:off + part.size] = part, True
+    return buf, defined, goff, doff
+
+
+def test_packed_collate_bytes_of_all_three_kinds(scale_set):
+    """An uncropped, a cropped and a scaled pack, every defined byte against a buffer assembled here."""
+    from can_distributed_pytorch_amd.ops.preprocess import PackedCollate
+    img_dir, gt_dir, imgs, _ = scale_set
+    K = 2
+    kw = dict(seed=SEED, raw=True)
+    # uncropped: two images that resize to the same 32 x 48 (the 37 x 53 one of the set and a 39 x 50 x 4 one)
+    rng = np.random.default_rng(2)
+    im_a, g_a, fl_a = CrowdDataset(img_dir, gt_dir, D, "train", **kw)[1]
+    im_b, g_b = torch.from_numpy(rng.integers(0, 256, (39, 50, 4), dtype=np.uint8)), torch.from_numpy(
+        rng.random((1, 4, 6)).astype(np.float32))
+    buf, meta = PackedCollate()([(im_a, g_a, fl_a), (im_b, g_b, True)])
+    want, defined, goff, doff = _assemble([im_a, im_b], torch.stack([g_a, g_b]).numpy(),
+                                          [[0, 37, 53, 3, int(fl_a), 0, 0, 0], [37 * 53 * 3, 39, 50, 4, 1, 0, 0, 0]])
+    assert meta == (2, 32, 48, goff, doff) and buf.numel() == want.size
+    assert np.array_equal(buf.numpy()[defined], want[defined])
+    for scaled in (False, True):
+        ds = CrowdDataset(img_dir, gt_dir, D, "train", crop=CROP, crops_per_image=K,
+                          crop_scale=SCALE if scaled else None, **kw)
+        items = [ds[2], ds[0], ds[3]]
+        buf, meta = PackedCollate(crop=CROP, crop_scale=scaled)(items)
+        rows, off = [], 0
+        for img, _, wins in items:
+            for w in wins.tolist():
+                rows.append([off, img.shape[0], img.shape[1], 3, w[2], w[0], w[1], (w[3] << 32) | w[4] if scaled else 1])
+            off += img.numel()
+        want, defined, goff, doff = _assemble([it[0] for it in items], torch.cat([it[1] for it in items]).numpy(), rows)
+        assert meta == (3 * K, *CROP, goff, doff, 3) + ((1,) if scaled else ()) and buf.numel() == want.size
+        assert np.array_equal(buf.numpy()[defined], want[defined])
 
 
 # ---------------------------------------------------------------- train.py
