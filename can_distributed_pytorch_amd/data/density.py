@@ -76,7 +76,12 @@ def gaussian_filter_density(img_or_shape, points: Union[np.ndarray, Sequence]) -
 
 
 def density_map_gpu(points, h: int, w: int, device="cuda", max_radius: int = 0) -> torch.Tensor:
-    """GPU density map [h, w] fp32 for points [[x, y], ...]."""
+    """GPU density map [h, w] fp32 for points [[x, y], ...].  Not bitwise reproducible (fp32 atomics); measured on
+    one MI355X against an fp64 reference (tests/test_gpu_density.py): the kNN sigma within 0.34 * 8 * 2^-24 relative,
+    each head's contribution within 2.8 * 2^-24 * (1 + |a_y| + |a_x|) of itself, a the exponent of the Gaussian
+    factor (about 8 at the edge of a footprint, more for a sigma below 1); the worst relative error of an element
+    inside a footprint was 3.8e-7 for sigma-4 heads and 2.2e-6 over all cases.  The tests hold the kernel to
+    20 * 2^-24 * (1 + |a_y| + |a_x|)."""
     from ..ops import _ext
     C = _ext.require()
     pts = torch.as_tensor(np.asarray(points, dtype=np.float32).reshape(-1, 2), device=device).contiguous()

@@ -81,8 +81,14 @@ def make_synthetic_batch_gpu(batch: int, h: int, w: int, seed: int = 0, device="
     """The same recipe rendered on the GPU (csrc/preprocess.hip synth_render + the density splat of
     csrc/density.hip): only the head points and a coarse noise grid are drawn on the host.  Returns
     (x4 [B,H,W,4] 16-bit NHWC4 — the first layer's input layout — or, nhwc4=False, img [B,3,H,W] fp32,
-    gt [B,1,H/8,W/8] fp32).  Statistically the CPU generator's images; not bitwise (different resampling
-    order), and reproducible per seed to fp32 rounding only (the density splat adds with fp32 atomics).  seeds: optional per-image seeds (image i a function of seeds[i] alone: sharded datasets)."""
+    gt [B,1,H/8,W/8] fp32).  For batch = 1 (or per-image seeds) this is the CPU recipe
+    make_synthetic_batch(1, h, w, seed) element by element, not bitwise: the head count, the points and the noise
+    grid are drawn from the generator in the same order, the ground truth is within the pooled splat bound +
+    128 * 2^-24 of each cell's sum, the image within half a 16-bit ulp + 14 * 2^-24 / std_c + the splat bound through
+    0.3 / (dmax + 1e-6) / std_c of the fp64 recipe (tests/density_reference.py, tests/test_gpu_density.py; the fp32
+    CPU recipe is within 2e-6 of the same reference).  Reproducible per seed to fp32 rounding only (the density splat
+    adds with fp32 atomics).  seeds: optional per-image seeds (image i a function of seeds[i] alone: sharded
+    datasets)."""
     from ..ops import _ext
     from ..ops.conv import dt_code
     C = _ext.require()
