@@ -112,6 +112,13 @@ int can_ctx_bwd_final(const void* dcat, const void* dc, const float* dave, const
 // density.hip
 int can_density_map(const float* pts, int n, int H, int W, float* sigma_ws, float* out, int max_r, void* stream,
                     float fixed_sigma);
+// ground truth of crop windows from head records (c, r, sigma, R): exact area sums, no atomics, table order.  The check
+// reads host memory only and launches nothing; can_gt_from_heads runs it first and returns its code.
+int can_gt_from_heads_check(const float* heads_host, long long n_heads, const long long* ranges_host,
+                            const long long* desc_host, int n, int CH, int CW, int ds);
+int can_gt_from_heads(const float* heads, const long long* ranges, const long long* desc, const float* heads_host,
+                      long long n_heads, const long long* ranges_host, const long long* desc_host, int n, float* gt,
+                      int CH, int CW, int ds, void* stream);
 
 // preprocess.hip
 int can_preprocess_image(const void* img, int H0, int W0, int C, int flip, void* out, int Ho, int Wo, int dt,

@@ -20,6 +20,9 @@ offset and flip drawn by ``crop_draw`` from (seed, epoch, index, k), zero-padded
 where the image is smaller than the crop (README, "Random-crop training").
 ``crop_scale=(lo, hi)`` adds a random scale per crop (``scale_draw``): a window of
 (ch, cw) / s is resampled to the crop, never padded (README, "Random-scale crops").
+``gt_from_heads=True`` (with ``crop``) renders every crop's ground truth from the image's head records
+(``IMG_k.heads.npy``, data/density.py:heads_table) as exact area sums instead of resampling the density map, which
+is then never opened (README, "Ground truth from heads").
 ``SyntheticCrowdDataset`` provides the same item contract without files
 (benchmarks, tests, smoke runs).
 """
@@ -32,7 +35,8 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from .transforms import _axis_weights, area_factor, prepare_pair, prepare_pair_scaled
+from .transforms import (_axis_weights, area_factor, heads_to_gt, heads_to_gt_padded, prepare_pair,
+                         prepare_pair_scaled)
 
 IMG_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".tif", ".tiff")
 _M64 = (1 << 64) - 1
@@ -194,7 +198,7 @@ def imread(path: str) -> np.ndarray:
 class CrowdDataset(Dataset):
     def __init__(self, img_root: str, gt_dmap_root: str, gt_downsample: int = 1, phase: str = "train",
                  seed: Optional[int] = None, raw: bool = False, crop=None, crops_per_image: int = 1,
-                 crop_scale=None):
+                 crop_scale=None, gt_from_heads: bool = False):
         self.img_root = img_root
         self.gt_dmap_root = gt_dmap_root
         self.gt_downsample = max(1, int(gt_downsample))
@@ -226,6 +230,10 @@ class CrowdDataset(Dataset):
             lo_hi = check_crop_scale(*crop_scale)
             if self.crop is not None:
                 self.crop_scale = lo_hi
+        # gt_from_heads: the crops' ground truth is rendered from the head sidecars (exact area sums), no map is opened
+        if gt_from_heads and crop is None:
+            raise ValueError("gt_from_heads needs crop=(ch, cw): it renders the ground truth of crop windows")
+        self.gt_from_heads = bool(gt_from_heads) and self.crop is not None
 
     def __len__(self):
         return self.n_samples
@@ -236,6 +244,18 @@ class CrowdDataset(Dataset):
     def gt_path(self, name: str) -> str:
         stem = os.path.splitext(name)[0]
         return os.path.join(self.gt_dmap_root, stem + ".npy")
+
+    def load_heads(self, name: str) -> np.ndarray:
+        """The head records float32 [N, 4] of image ``name`` from its sidecar next to the density map."""
+        from .density import heads_path
+        path = heads_path(self.gt_path(name))
+        if not os.path.isfile(path):
+            raise ValueError(f"{name}: no head sidecar {path}; write the sidecars with "
+                             "`python data_preparation/k_nearest_gaussian_kernel.py <dataset root> --heads`")
+        heads = np.load(path)                                    # allow_pickle=False (default)
+        if heads.ndim != 2 or heads.shape[1] != 4:
+            raise ValueError(f"{path}: head records must be [N, 4] of (c, r, sigma, R), got {tuple(heads.shape)}")
+        return np.ascontiguousarray(heads, dtype=np.float32)
 
     def __getitem__(self, index):
         epoch = self.epoch
@@ -266,14 +286,18 @@ class CrowdDataset(Dataset):
         raw=False: ([K,3,ch,cw] f32, [K,1,ch/d,cw/d] f32), each prepare_pair / prepare_pair_scaled of the window's
         slices.  raw=True: (uint8 image, [K,1,ch/d,cw/d] f32, int64 windows [K,3] of (y0, x0, flip) or, scaled, [K,5]
         of (y0, x0, flip, sh, sw)): the GPU cuts the windows (ops/preprocess.py), the ground truths are made here from
-        the memory-mapped map."""
+        the memory-mapped map.  gt_from_heads: the same windows; raw=False renders each ground truth with heads_to_gt /
+        heads_to_gt_padded, raw=True returns the image's head records [N, 4] in place of the K ground truths (the GPU
+        renders them); no density map is opened."""
         d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
         h0, w0 = img.shape[:2]
+        scaled = self.crop_scale is not None
+        if self.gt_from_heads:
+            return self._crop_item_heads(img, self.load_heads(name), epoch, index, scaled)
         dmap = np.load(self.gt_path(name), mmap_mode="r" if self.raw else None)      # allow_pickle=False (default)
         if tuple(dmap.shape) != (h0, w0):
             raise ValueError(f"{name}: density map {tuple(dmap.shape)} differs from its image {(h0, w0)}: a crop "
                              "takes the same window of both")
-        scaled = self.crop_scale is not None
         ims, gts, rows = [], [], []
         for k in range(K):
             if scaled:
@@ -293,6 +317,29 @@ class CrowdDataset(Dataset):
         if self.raw:
             return torch.from_numpy(_as_uint8(img)), gts, torch.tensor(rows, dtype=torch.int64)
         return torch.from_numpy(np.stack(ims)), gts
+
+    def _crop_item_heads(self, img: np.ndarray, heads: np.ndarray, epoch: int, index: int, scaled: bool):
+        """_crop_item with the ground truth from head records: the windows and flips are the same draws."""
+        d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
+        h0, w0 = img.shape[:2]
+        ims, gts, rows = [], [], []
+        for k in range(K):
+            if scaled:
+                wh, ww = scaled_window(h0, w0, ch, cw, scale_draw(self.seed, epoch, index, k, *self.crop_scale))
+            else:
+                wh, ww = crop_window(h0, w0, ch, cw, d)
+            y0, x0, fl = crop_draw(self.seed, epoch, index, k, h0 - wh + 1, w0 - ww + 1)
+            rows.append([y0, x0, int(fl)] + ([wh, ww] if scaled else []))
+            if self.raw:
+                continue
+            im, zero = img[y0:y0 + wh, x0:x0 + ww], np.zeros((wh, ww), dtype=np.float32)
+            im, _ = prepare_pair_scaled(im, zero, ch, cw, d, fl) if scaled else prepare_pair(im, zero, d, fl)
+            ims.append(_pad_to(im, ch, cw))
+            gts.append(heads_to_gt(heads, h0, w0, (y0, x0, wh, ww), ch, cw, d, fl) if scaled else
+                       heads_to_gt_padded(heads, h0, w0, y0, x0, ch, cw, d, fl))
+        if self.raw:
+            return torch.from_numpy(_as_uint8(img)), torch.from_numpy(heads), torch.tensor(rows, dtype=torch.int64)
+        return torch.from_numpy(np.stack(ims)), torch.from_numpy(np.stack(gts))
 
 
 class SyntheticCrowdDataset(Dataset):

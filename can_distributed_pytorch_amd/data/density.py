@@ -11,6 +11,8 @@ Reference: data_preparation/k_nearest_gaussian_kernel.py:14-92.
   scipy.ndimage.gaussian_filter(delta, sigma, mode='constant') (truncate 4).
 * ``density_map_gpu(points, H, W)`` — the same on the GPU (csrc/density.hip:
   brute-force kNN + per-head splat).
+* ``heads_table(points, shape)`` — the head records (c, r, sigma, R) the map is a sum over; ``--heads`` writes them
+  as ``IMG_*.heads.npy`` sidecars, from which ``--gt-from-heads`` renders crop ground truth as exact area sums.
 * ``generate_dataset_density(root)`` — the offline driver (ShanghaiTech layout:
   images/*.jpg + ground_truth/GT_IMG_*.mat -> ground_truth/IMG_*.npy).
 """
@@ -75,6 +77,28 @@ def gaussian_filter_density(img_or_shape, points: Union[np.ndarray, Sequence]) -
     return density.astype(np.float32)
 
 
+def heads_table(points: Union[np.ndarray, Sequence], shape) -> np.ndarray:
+    """The head records of an image, float32 [N, 4] of (c, r, sigma, R): what ``gaussian_filter_density`` splats, kept
+    instead of the map.  c, r = int(x), int(y), the pixel the delta goes to (out-of-image heads are dropped, as there;
+    they still count as neighbours of the others); sigma the float32 rounding of the float64 ``knn_sigmas`` value;
+    R = int(4 sigma64 + 0.5), from the float64 sigma and STORED: no later stage recomputes a radius from the rounded
+    sigma.  sigma <= 0 (coincident heads) is a unit delta, R = 0."""
+    h, w = _shape_of(shape)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    rows = []
+    for (x, y), s in zip(pts, knn_sigmas(pts, (h, w))):
+        if x < 0 or y < 0 or int(y) >= h or int(x) >= w:
+            continue
+        s = float(s)
+        rows.append((int(x), int(y), s, int(4.0 * s + 0.5)) if s > 0 else (int(x), int(y), 0.0, 0))
+    return np.asarray(rows, dtype=np.float32).reshape(-1, 4)
+
+
+def heads_path(npy_path: str) -> str:
+    """ground_truth/IMG_k.npy -> ground_truth/IMG_k.heads.npy, the sidecar of ``--heads``."""
+    return os.path.splitext(npy_path)[0] + ".heads.npy"
+
+
 def density_map_gpu(points, h: int, w: int, device="cuda", max_radius: int = 0) -> torch.Tensor:
     """GPU density map [h, w] fp32 for points [[x, y], ...].  Not bitwise reproducible (fp32 atomics); measured on
     one MI355X against an fp64 reference (tests/test_gpu_density.py): the kNN sigma within 0.34 * 8 * 2^-24 relative,
@@ -101,8 +125,11 @@ def load_sha_points(mat_path: str) -> np.ndarray:
     return np.asarray(mat["image_info"][0, 0][0, 0][0], dtype=np.float64)
 
 
-def generate_dataset_density(root: str, parts=("train_data", "test_data"), use_gpu: bool = False) -> int:
-    """Offline driver (reference :58-92): writes ground_truth/IMG_k.npy next to images/IMG_k.jpg."""
+def generate_dataset_density(root: str, parts=("train_data", "test_data"), use_gpu: bool = False,
+                             heads: bool = False) -> int:
+    """Offline driver (reference :58-92): writes ground_truth/IMG_k.npy next to images/IMG_k.jpg.  heads=True writes
+    the head sidecars ground_truth/IMG_k.heads.npy (``heads_table``) INSTEAD: run it over a dataset whose maps exist, or
+    after the plain run; without it exactly the files of the plain run are written."""
     from .dataset import imread
     count = 0
     for part in parts:
@@ -110,13 +137,14 @@ def generate_dataset_density(root: str, parts=("train_data", "test_data"), use_g
             mat = img_path.replace(".jpg", ".mat").replace("images", "ground_truth").replace("IMG_", "GT_IMG_")
             img = imread(img_path)
             pts = load_sha_points(mat)
-            if use_gpu and torch.cuda.is_available():
-                d = density_map_gpu(pts, img.shape[0], img.shape[1]).cpu().numpy()
-            else:
-                d = gaussian_filter_density(img, pts)
             out = img_path.replace(".jpg", ".npy").replace("images", "ground_truth")
             os.makedirs(os.path.dirname(out), exist_ok=True)
-            np.save(out, d)
+            if heads:
+                np.save(heads_path(out), heads_table(pts, img.shape[:2]))
+            elif use_gpu and torch.cuda.is_available():
+                np.save(out, density_map_gpu(pts, img.shape[0], img.shape[1]).cpu().numpy())
+            else:
+                np.save(out, gaussian_filter_density(img, pts))
             count += 1
     return count
 
@@ -126,5 +154,7 @@ if __name__ == "__main__":  # pragma: no cover
     ap = argparse.ArgumentParser(description="generate geometry-adaptive density maps (ShanghaiTech layout)")
     ap.add_argument("root")
     ap.add_argument("--gpu", action="store_true")
+    ap.add_argument("--heads", action="store_true",
+                    help="write the head sidecars IMG_k.heads.npy (for train.py --gt-from-heads) instead of the maps")
     a = ap.parse_args()
-    print(generate_dataset_density(a.root, use_gpu=a.gpu), "maps written")
+    print(generate_dataset_density(a.root, use_gpu=a.gpu, heads=a.heads), "head tables" if a.heads else "maps", "written")

@@ -108,3 +108,70 @@ def prepare_pair_scaled(img: np.ndarray, dmap: np.ndarray, ch: int, cw: int, dow
     img = resize_linear(np.ascontiguousarray(img), cw, ch)
     dm = resize_linear(np.ascontiguousarray(dmap, dtype=np.float32), cols, rows) * area_factor(sh, sw, rows, cols)
     return normalize_chw(img), dm[None].astype(np.float32)
+
+
+def _cell_overlaps(ext: int, cells: int, lo: int, hi: int) -> np.ndarray:
+    """[cells, hi - lo] float64: the length of source pixel p (lo <= p < hi, window-relative) inside cell i of an axis
+    of extent ``ext`` cut into ``cells`` cells: max(0, min((p+1) cells, (i+1) ext) - max(p cells, i ext)) / cells, the
+    integers exact."""
+    p = np.arange(lo, hi, dtype=np.int64)[None, :]
+    i = np.arange(cells, dtype=np.int64)[:, None]
+    return np.maximum(0, np.minimum((p + 1) * cells, (i + 1) * ext) - np.maximum(p * cells, i * ext)) / float(cells)
+
+
+def _head_profile(pos: int, sigma: float, radius: int, off: int, ext: int, cells: int) -> np.ndarray:
+    """P[i] = sum_p overlap_i(p) k[off + p - pos] over the window pixels p inside the head's footprint, k the
+    normalised, truncated 1-D Gaussian of the head record (a unit delta for sigma <= 0), float64 [cells]."""
+    if not sigma > 0:
+        radius = 0
+    lo, hi = max(0, pos - radius - off), min(ext, pos + radius + 1 - off)
+    if lo >= hi:
+        return np.zeros(cells)
+    if radius == 0:
+        k = np.ones(1)
+    else:
+        t = np.arange(-radius, radius + 1, dtype=np.float64)
+        k = np.exp(-(t * t) / (2.0 * sigma * sigma))
+        k = k / k.sum()
+    return _cell_overlaps(ext, cells, lo, hi) @ k[lo + off - pos + radius:hi + off - pos + radius]
+
+
+def heads_to_gt64(heads: np.ndarray, h0: int, w0: int, window, ch: int, cw: int, downsample: int = 8,
+                  flip: bool = False) -> np.ndarray:
+    """heads_to_gt before its float32 rounding: float64 [ch/d, cw/d]."""
+    y0, x0, sh, sw = (int(v) for v in window)
+    if downsample < 1 or ch <= 0 or cw <= 0 or ch % downsample or cw % downsample:
+        raise ValueError(f"sample {ch}x{cw} must be a positive multiple of the downsample {downsample}")
+    if sh < 1 or sw < 1 or y0 < 0 or x0 < 0 or y0 + sh > h0 or x0 + sw > w0:
+        raise ValueError(f"window {(y0, x0, sh, sw)} is empty or leaves its {h0}x{w0} image")
+    rows, cols = ch // downsample, cw // downsample
+    out = np.zeros((rows, cols), dtype=np.float64)
+    for c, r, sigma, radius in np.asarray(heads, dtype=np.float32).reshape(-1, 4).tolist():
+        c, r, radius = int(c), int(r), int(radius)
+        if r + radius < y0 or r - radius >= y0 + sh or c + radius < x0 or c - radius >= x0 + sw:
+            continue                             # the footprint misses the window: exactly nothing
+        out += np.outer(_head_profile(r, sigma, radius, y0, sh, rows), _head_profile(c, sigma, radius, x0, sw, cols))
+    return out[:, ::-1] if flip else out
+
+
+def heads_to_gt(heads: np.ndarray, h0: int, w0: int, window, ch: int, cw: int, downsample: int = 8,
+                flip: bool = False) -> np.ndarray:
+    """The ground truth of a window rendered from head records (data/density.py:heads_table), no map resampled:
+    cell (i, j) of the (ch/d, cw/d) grid is the exact area sum of the density map over the source rectangle it
+    covers in window = (y0, x0, sh, sw), every source pixel a unit square of constant density, so the cells sum to
+    the window's density mass for any scale, offset and flip, and no area factor is applied.  Per head the sum is
+    separable, Py[i] Px[j]; heads are summed in table order in float64.  Returns fp32 [1, ch/d, cw/d]."""
+    return heads_to_gt64(heads, h0, w0, window, ch, cw, downsample, flip)[None].astype(np.float32)
+
+
+def heads_to_gt_padded(heads: np.ndarray, h0: int, w0: int, y0: int, x0: int, ch: int, cw: int, downsample: int = 8,
+                       flip: bool = False) -> np.ndarray:
+    """heads_to_gt for the UNSCALED crop at (y0, x0): the valid (vh, vw) = crop_window extent of the crop is rendered
+    (every cell an exact d x d box sum, flipped within the valid columns) and the cells of the zero padding of an image
+    smaller than the crop are 0.  Returns fp32 [1, ch/d, cw/d]."""
+    d = downsample
+    vh, vw = min(ch, h0 // d * d), min(cw, w0 // d * d)
+    out = np.zeros((1, ch // d, cw // d), dtype=np.float32)
+    if vh and vw:
+        out[:, :vh // d, :vw // d] = heads_to_gt(heads, h0, w0, (y0, x0, vh, vw), vh, vw, d, flip)
+    return out

@@ -12,8 +12,12 @@ ONE kernel launch turns the batch into network inputs (``preprocess_packed``).
 ``PackedCollate(crop=(ch, cw))`` packs random-crop batches: every image once,
 one descriptor per crop, cut on the GPU by one launch of the crop kernel;
 with ``crop_scale=True`` every descriptor carries its window's extent and the
-resize launch's kernel resamples it to the crop.  A pack of any kind goes
-through one collate loop, ``_unpack`` and ``_launch``.
+resize launch's kernel resamples it to the crop.  With ``gt_from_heads=True``
+a cropped pack carries the images' head records instead of ground-truth
+values and a second launch on the same stream (csrc/density.hip,
+gt_from_heads_kernel) renders the ground truth region of the buffer from
+them.  A pack of any kind goes through one collate loop, ``_unpack`` and
+``_launch``.
 """
 from __future__ import annotations
 
@@ -72,13 +76,21 @@ class PackedCollate:
     and one descriptor per output sample, desc = (image byte offset, H0, W0, C, flip, y0, x0, 1) -- the K crops of an
     image share its offset.  The meta tuple gains a sixth field, the number of images, which marks the pack as cropped.
     crop_scale=True: the windows are [K,5] of (y0, x0, flip, sh, sw), slot 7 of a descriptor is (sh << 32) | sw (never
-    the unscaled 1) and the meta tuple gains a seventh field, 1, which marks the pack as scaled."""
+    the unscaled 1) and the meta tuple gains a seventh field, 1, which marks the pack as scaled.
+    gt_from_heads=True (with crop, scaled or not): for CrowdDataset(raw=True, crop=..., gt_from_heads=True) items
+    (uint8 image, head records [N,4] fp32, windows).  The ground truth region is zero (the GPU renders it in place),
+    and behind the descriptors follow the int64 ranges [n, 2] = (first head, head count) of every output sample -- the
+    K crops of an image share one range -- and the head table [sum N, 4] fp32, both 16-byte aligned.  The meta tuple
+    has eight fields, (..., images, scaled 0 / 1, heads in the table), a length no other kind has."""
 
-    def __init__(self, downsample: int = 8, crop=None, crop_scale=False):
+    def __init__(self, downsample: int = 8, crop=None, crop_scale=False, gt_from_heads=False):
         self.ds = downsample
         self.crop_scale = bool(crop_scale)
+        self.gt_from_heads = bool(gt_from_heads)
         if self.crop_scale and crop is None:
             raise ValueError("crop_scale needs crop=(ch, cw)")
+        if self.gt_from_heads and crop is None:
+            raise ValueError("gt_from_heads needs crop=(ch, cw)")
         self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
         if self.crop is not None and (min(self.crop) <= 0 or self.crop[0] % downsample or self.crop[1] % downsample):
             raise ValueError(f"crop {self.crop} must be a positive multiple of the downsample {downsample}")
@@ -93,7 +105,11 @@ class PackedCollate:
                 raise ValueError("raw samples must carry the 1/d ground truth [1, H/d, W/d]")
             return [(int(bool(third)), 0, 0, 0)]
         nw = 5 if self.crop_scale else 3
-        if g.dim() != 4 or tuple(g.shape[1:]) != (1, ho // d, wo // d) or tuple(third.shape) != (g.shape[0], nw):
+        if self.gt_from_heads:
+            if g.dim() != 2 or g.shape[1] != 4 or g.dtype != torch.float32 or third.dim() != 2 or third.shape[1] != nw:
+                raise ValueError(f"cropped raw samples with gt_from_heads must carry head records [N, 4] fp32 and "
+                                 f"windows [K, {nw}]")
+        elif g.dim() != 4 or tuple(g.shape[1:]) != (1, ho // d, wo // d) or tuple(third.shape) != (g.shape[0], nw):
             raise ValueError(f"cropped raw samples must carry ground truths [K, 1, ch/d, cw/d] and windows [K, {nw}]")
         if not self.crop_scale:
             return [(fl, y0, x0, 1) for y0, x0, fl in third.tolist()]
@@ -102,18 +118,21 @@ class PackedCollate:
         return [(fl, y0, x0, (sh << 32) | sw) for y0, x0, fl, sh, sw in third.tolist()]
 
     @staticmethod
-    def _fill(imgs, ioff, gt, desc):
-        """One buffer: the images back to back | the ground truth at goff | the descriptors at doff (16-byte aligned)."""
+    def _fill(imgs, ioff, gt, desc, tail=None):
+        """One buffer: the images back to back | the ground truth at goff | the descriptors at doff (16-byte aligned),
+        then ``tail`` (the ranges and the head table of a heads pack, a multiple of 16 bytes after 64 n)."""
         goff = -(-ioff // 16) * 16
         doff = -(-(goff + 4 * gt.numel()) // 16) * 16
-        buf = torch.empty(doff + 8 * desc.numel(), dtype=torch.uint8)
+        buf = torch.empty(doff + 8 * desc.numel() + (0 if tail is None else tail.numel()), dtype=torch.uint8)
         o = 0
         for im in imgs:
             k = im.numel()
             buf[o:o + k] = im.reshape(-1)
             o += k
         buf[goff:goff + 4 * gt.numel()] = gt.reshape(-1).view(torch.uint8)
-        buf[doff:] = desc.reshape(-1).view(torch.uint8)
+        buf[doff:doff + 8 * desc.numel()] = desc.reshape(-1).view(torch.uint8)
+        if tail is not None:
+            buf[doff + 8 * desc.numel():] = tail
         return buf, goff, doff
 
     def __call__(self, batch: List):
@@ -122,13 +141,23 @@ class PackedCollate:
             ho, wo = (imgs[0].shape[0] // self.ds) * self.ds, (imgs[0].shape[1] // self.ds) * self.ds
         else:
             ho, wo = self.crop
-        rows, ioff = [], 0
+        rows, ranges, ioff, hoff = [], [], 0, 0
         for im, g, third in zip(imgs, gts, thirds):
             hh, ww = im.shape[:2]
             c = 1 if im.dim() == 2 else im.shape[2]
-            rows += [[ioff, hh, ww, c, *w] for w in self._windows(im, g, third, ho, wo)]
+            wins = self._windows(im, g, third, ho, wo)
+            rows += [[ioff, hh, ww, c, *w] for w in wins]
             ioff += hh * ww * c
+            if self.gt_from_heads:
+                ranges += [[hoff, g.shape[0]]] * len(wins)
+                hoff += g.shape[0]
         desc = torch.tensor(rows, dtype=torch.int64)
+        if self.gt_from_heads:
+            gt = torch.zeros(len(rows), 1, ho // self.ds, wo // self.ds)
+            tail = torch.cat([torch.tensor(ranges, dtype=torch.int64).reshape(-1).view(torch.uint8),
+                              torch.cat(gts).contiguous().reshape(-1).view(torch.uint8)])
+            buf, goff, doff = self._fill(imgs, ioff, gt, desc, tail)
+            return buf, (len(rows), ho, wo, goff, doff, len(imgs), int(self.crop_scale), hoff)
         gt = (torch.stack(gts) if self.crop is None else torch.cat(gts)).float().contiguous()
         buf, goff, doff = self._fill(imgs, ioff, gt, desc)
         kind = () if self.crop is None else (len(imgs), 1) if self.crop_scale else (len(imgs),)
@@ -141,13 +170,20 @@ KINDS = ("batch", "crop", "crop_scaled")         # a pack's kind: the C.preproce
 def _unpack(packed):
     """(buf, (n, Ho, Wo, gt_offset, desc_offset), kind) of a PackedCollate output, kind one of KINDS: a cropped
     pack's meta tuple carries a sixth field (its number of images) and n counts output samples, one descriptor each;
-    a scaled pack's carries a seventh, 1."""
+    a scaled pack's carries a seventh, 1.  A heads pack's meta tuple has eight fields (images, scaled 0 / 1, heads):
+    its kind is "crop+heads" or "crop_scaled+heads", and its buffer ends with the ranges and the head table."""
     buf, meta = packed
     n, ho, wo, goff, doff = meta[:5]
-    meta_ok = len(meta) in (5, 6) or (len(meta) == 7 and meta[6] == 1)
-    buf_ok = buf.dtype == torch.uint8 and buf.dim() == 1 and buf.numel() == doff + 64 * n
+    heads = len(meta) == 8
+    meta_ok = len(meta) in (5, 6) or (len(meta) == 7 and meta[6] == 1) or \
+        (heads and meta[6] in (0, 1) and meta[7] >= 0)
+    size = doff + 64 * n + ((16 * n + 16 * meta[7]) if heads and meta_ok else 0)
+    buf_ok = buf.dtype == torch.uint8 and buf.dim() == 1 and buf.numel() == size
     if not (meta_ok and buf_ok) or goff % 16 or doff % 16:
-        raise ValueError("packed batch: one uint8 buffer (images | fp32 ground truth | int64 descriptors)")
+        raise ValueError("packed batch: one uint8 buffer (images | fp32 ground truth | int64 descriptors"
+                         " [| int64 head ranges | fp32 head records])")
+    if heads:
+        return buf, (n, ho, wo, goff, doff), KINDS[1 + meta[6]] + "+heads"
     return buf, (n, ho, wo, goff, doff), KINDS[len(meta) - 5]
 
 
@@ -156,14 +192,27 @@ def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device):
     check the host descriptors (in buf) before they launch."""
     hd, wd = ho // downsample, wo // downsample
     gt = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
-    desc = d[doff:].view(torch.int64).view(n, 8)
+    desc = d[doff:doff + 64 * n].view(torch.int64).view(n, 8)
     x4 = torch.empty(n, ho, wo, 4, dtype=dtype, device=device)
     tail = (ho, wo, downsample, dt_code(dtype), _ext.stream_ptr(device))
+    kind, _, heads = kind.partition("+")
+    if heads:
+        # checked on the host copies before EITHER launch (a refused pack launches nothing); the render itself is
+        # issued right after the image launch, on the same stream
+        roff, hoff = doff + 64 * n, doff + 80 * n
+        nh = (buf.numel() - hoff) // 16
+        rc = C.gt_from_heads_check(buf.data_ptr() + hoff, nh, buf.data_ptr() + roff, buf.data_ptr() + doff, n, ho, wo,
+                                   downsample)
+        if rc:
+            raise RuntimeError(f"gt_from_heads refused the pack (code {rc})")
     if kind == "batch":
         C.preprocess_batch(d.data_ptr(), 0, desc.data_ptr(), n, x4.data_ptr(), 0, *tail)
     else:
         getattr(C, "preprocess_" + kind)(d.data_ptr(), goff, desc.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(),
                                          *tail)
+    if heads:
+        C.gt_from_heads(d.data_ptr() + hoff, d.data_ptr() + roff, desc.data_ptr(), buf.data_ptr() + hoff, nh,
+                        buf.data_ptr() + roff, buf.data_ptr() + doff, n, gt.data_ptr(), ho, wo, downsample, tail[-1])
     return x4, gt
 
 

@@ -107,6 +107,8 @@ class _Parser(argparse.ArgumentParser):
             self.error("--crop-size crops decoded dataset images; it cannot be combined with --synthetic")
         if ns.crop_scale is not None and ns.crop_size is None:
             self.error("--crop-scale rescales the windows of --crop-size; give --crop-size as well")
+        if ns.gt_from_heads and ns.crop_size is None:
+            self.error("--gt-from-heads renders the ground truth of the crops of --crop-size; give --crop-size as well")
         return ns
 
 
@@ -198,6 +200,12 @@ def build_parser():
                         "e.g. 0.75,1.33) and resamples a window of the crop size / s to the crop (s > 1 magnifies), "
                         "bilinearly, the density rescaled by the area ratio.  The window always fits: an image smaller "
                         "than the crop is upsampled to fill it, not padded.  Default: off")
+    p.add_argument("--gt-from-heads", action="store_true",
+                   help="with --crop-size (with or without --crop-scale): render every crop's ground truth from the "
+                        "image's head records (ground_truth/IMG_k.heads.npy, written by data_preparation/"
+                        "k_nearest_gaussian_kernel.py <root> --heads) as exact area sums of the density map, on the GPU "
+                        "with --gpu-preprocess, instead of point-sampling the map: a cell holds its window's density "
+                        "mass at any scale.  Default: off")
     p.add_argument("--log-every", type=int, default=20,
                    help="steps between the training records of --log-jsonl (each reads the loss back: a host sync)")
     return p
@@ -217,7 +225,8 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
     if crop is not None:
         # every training sample is a crop of one size; test images stay whole and of mixed size: batch 1
         from can_distributed_pytorch_amd.data.dataset import crop_collate
-        train_collate = PackedCollate(crop=crop, crop_scale=args.crop_scale is not None) if raw else crop_collate
+        train_collate = PackedCollate(crop=crop, crop_scale=args.crop_scale is not None,
+                                      gt_from_heads=args.gt_from_heads) if raw else crop_collate
         eval_batch = 1
     if args.synthetic:
         h, w = (int(v) for v in args.synthetic.lower().split("x"))
@@ -228,7 +237,7 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
         train_ds = CrowdDataset(os.path.join(r, "train_data", "images"), os.path.join(r, "train_data", "ground_truth"),
                                 gt_downsample=8, phase="train", seed=args.seed, raw=raw, crop=crop,
                                 crops_per_image=args.crops_per_image if crop is not None else 1,
-                                crop_scale=args.crop_scale)
+                                crop_scale=args.crop_scale, gt_from_heads=args.gt_from_heads)
         test_ds = CrowdDataset(os.path.join(r, "test_data", "images"), os.path.join(r, "test_data", "ground_truth"),
                                gt_downsample=8, phase="test", raw=raw)
     train_sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed)
@@ -394,6 +403,7 @@ def main(args):
                     **(dict(crop_size=list(args.crop_size), crops_per_image=args.crops_per_image,
                             eval_batch_size=test_loader.batch_size) if args.crop_size is not None else {}),
                     **(dict(crop_scale=list(args.crop_scale)) if args.crop_scale is not None else {}),
+                    **(dict(gt_from_heads=True) if args.gt_from_heads else {}),
                     **(dict(ema_decay=args.ema_decay) if ema_on else {}))
             if use_wandb:
                 wandb_log(loss=mean_loss, mae=mean_mae, lr=lr_now)
