@@ -139,6 +139,14 @@ int can_preprocess_crop(const void* imgs, long long img_bytes, const long long* 
 int can_preprocess_crop_scaled(const void* imgs, long long img_bytes, const long long* desc,
                                const long long* desc_host, int n, void* x4, int CH, int CW, int ds, int dt,
                                void* stream);
+// either crop launch (scaled == 0: can_preprocess_crop, else can_preprocess_crop_scaled) with photometric jitter: photo,
+// float [n][260] on the device (16-byte aligned) and photo_host on the host, one row per output sample of 256 tone-table
+// entries on the 0..255 scale, the gray flag (0 / 1) and three zeros.  Every source byte goes through its sample's table
+// (and the luma mix where the flag is 1) before the resample.  Refuses what the plain entry refuses, a null or misaligned
+// photo, an entry that is not finite or leaves [0, 255] and any other flag, before the launch
+int can_preprocess_crop_photo(const void* imgs, long long img_bytes, const long long* desc, const long long* desc_host,
+                              int n, void* x4, int CH, int CW, int ds, int dt, void* stream, const float* photo,
+                              const float* photo_host, int scaled);
 // synthetic batch: full-res densities [n][H][W] + coarse noise [n][3][H/16][W/16] -> x4 NHWC4, gt [n][H/8][W/8]
 int can_synth_render(const float* dens, const float* noise, float* dmax, void* x4, float* gt, int n, int H, int W,
                      int dt, void* stream);

@@ -10,7 +10,9 @@
 // so the host only decodes JPEGs.
 //
 // Every kernel below is built from one set of helpers: lin_tap (the tap rule), blend4 (the four-tap blend),
-// imagenet / normalise / pack_px (ImageNet constants, x 1/255, NHWC4 words), resample_px (a whole pixel) and load_desc.
+// imagenet / normalise / pack_px (ImageNet constants, x 1/255, NHWC4 words), resample_px (a whole pixel) and load_desc; the
+// PHOTO instantiations of the crop kernels (photometric jitter) add load_photo and lut_tap (a source pixel's three values
+// through the sample's tone table).
 #include "common.h"
 
 namespace can {
@@ -46,18 +48,50 @@ __device__ __forceinline__ uint2 pack_px(const float (&v)[3]) {
   return make_uint2(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], 0.f));
 }
 
-// One output pixel of a uint8 image: tap rows ra / rb, tap pixels at byte offsets oa / ob of a row; gray (C == 1)
-// feeds all three channels.
-template <int DT>
-__device__ __forceinline__ uint2 resample_px(const unsigned char* ra, const unsigned char* rb, size_t oa, size_t ob,
-                                             int C, float fx, float fy) {
-  float v[3];
+// The row of floats per output sample of a photo pack: 256 tone-table entries on the 0..255 scale, the gray flag, 3 zeros.
+constexpr int PHOTO_ROW = 260;
+
+// PHOTO: the three channel values of one source pixel on the 0..255 scale.  Every byte goes through the sample's tone
+// table lut (LDS) instead of the int-to-float conversion; gray (C == 1) feeds all three channels; with mix a colour
+// pixel becomes its luma in all three (a 1-channel pixel is left alone).
+__device__ __forceinline__ void lut_tap(const unsigned char* px, int C, const float* lut, bool mix, float (&t)[3]) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int cc = (C == 1) ? 0 : c;
-    v[c] = normalise(blend4(ra[oa + cc], ra[ob + cc], rb[oa + cc], rb[ob + cc], fx, fy), c);
+  for (int c = 0; c < 3; ++c) t[c] = lut[px[(C == 1) ? 0 : c]];
+  if (mix && C != 1) t[0] = t[1] = t[2] = __fmaf_rn(0.114f, t[2], __fmaf_rn(0.587f, t[1], 0.299f * t[0]));
+}
+
+// One output pixel of a uint8 image: tap rows ra / rb, tap pixels at byte offsets oa / ob of a row; gray (C == 1)
+// feeds all three channels.  PHOTO: the four tap pixels are lut_tap's values.
+template <int DT, bool PHOTO = false>
+__device__ __forceinline__ uint2 resample_px(const unsigned char* ra, const unsigned char* rb, size_t oa, size_t ob,
+                                             int C, float fx, float fy, const float* lut = nullptr, bool mix = false) {
+  float v[3];
+  if constexpr (PHOTO) {
+    float a[3], b[3], d[3], e[3];
+    lut_tap(ra + oa, C, lut, mix, a);
+    lut_tap(ra + ob, C, lut, mix, b);
+    lut_tap(rb + oa, C, lut, mix, d);
+    lut_tap(rb + ob, C, lut, mix, e);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = normalise(blend4(a[c], b[c], d[c], e[c], fx, fy), c);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int cc = (C == 1) ? 0 : c;
+      v[c] = normalise(blend4(ra[oa + cc], ra[ob + cc], rb[oa + cc], rb[ob + cc], fx, fy), c);
+    }
   }
   return pack_px<DT>(v);
+}
+
+// A block's 256 threads bring their sample's (blockIdx.y's) tone table into lut, one entry each, and return the
+// sample's gray flag, a block-uniform value; the barrier stands ahead of the pixel loop.
+__device__ __forceinline__ bool load_photo(const float* __restrict__ photo, float* lut) {
+  const float* row = photo + (size_t)blockIdx.y * PHOTO_ROW;
+  lut[threadIdx.x] = row[threadIdx.x];
+  const bool mix = row[256] != 0.f;
+  __syncthreads();
+  return mix;
 }
 
 // Sample blockIdx.y's descriptor {image byte offset, H0, W0, C, flip, y0, x0, ext}: slots 5..7 are 0 for a whole
@@ -117,11 +151,17 @@ __global__ void __launch_bounds__(256) preprocess_density_kernel(const float* __
 // descriptors may share one image.  Output sample n = the window [y0, y0+vh) x [x0, x0+vw) of its image, vh =
 // min(CH, H0/ds*ds), vw = min(CW, W0/ds*ds), mirrored within the window when flipped, normalised, zero outside the
 // window (bottom / right padding of an image smaller than the crop).  A thread writes two adjacent NHWC4 pixels as
-// one 16-byte store (CW is even); it reads only bytes of the window.
-template <int DT>
+// one 16-byte store (CW is even); it reads only bytes of the window.  PHOTO (can_preprocess_crop_photo): every source
+// byte goes through the sample's tone table and gray mix (lut_tap); the padding stays zero.
+template <int DT, bool PHOTO = false, typename... Photo>
 __global__ void __launch_bounds__(256) preprocess_crop_kernel(const unsigned char* __restrict__ imgs,
                                                               const long long* __restrict__ desc,
-                                                              uint4* __restrict__ x4, int CH, int CW, int ds) {
+                                                              uint4* __restrict__ x4, int CH, int CW, int ds,
+                                                              Photo... photo) {
+  static_assert(sizeof...(Photo) == (PHOTO ? 1 : 0), "the photo region is the one extra argument of a PHOTO kernel");
+  __shared__ float lut[PHOTO ? 256 : 1];
+  bool mix = false;
+  if constexpr (PHOTO) mix = load_photo(photo..., lut);
   const Desc s = load_desc(desc);
   const int vh = min(CH, s.H0 / ds * ds), vw = min(CW, s.W0 / ds * ds);
   const unsigned char* img = imgs + s.off;
@@ -138,8 +178,14 @@ __global__ void __launch_bounds__(256) preprocess_crop_kernel(const unsigned cha
           const int sx = s.x0 + (s.flip ? vw - 1 - x : x);
           const unsigned char* px = img + ((size_t)(s.y0 + oy) * s.W0 + sx) * s.C;
           float v[3];
+          if constexpr (PHOTO) {
+            lut_tap(px, s.C, lut, mix, v);
 #pragma unroll
-          for (int c = 0; c < 3; ++c) v[c] = normalise((float)px[(s.C == 1) ? 0 : c], c);
+            for (int c = 0; c < 3; ++c) v[c] = normalise(v[c], c);
+          } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = normalise((float)px[(s.C == 1) ? 0 : c], c);
+          }
           w[p] = pack_px<DT>(v);
         }
       }
@@ -155,11 +201,17 @@ __global__ void __launch_bounds__(256) preprocess_crop_kernel(const unsigned cha
 // where it is (sh << 32) | sw (can_preprocess_crop_scaled); several descriptors may share one image.  No padding:
 // the whole sample is valid.  It reads only bytes of the window.  For sh == CH, sw == CW every fraction is exactly 0
 // and the blend returns the pixel itself, so the output is bitwise preprocess_crop_kernel's.  A thread writes two
-// adjacent NHWC4 pixels as one 16-byte store (CW is even).
-template <int DT>
+// adjacent NHWC4 pixels as one 16-byte store (CW is even).  PHOTO (can_preprocess_crop_photo): every tap pixel goes
+// through the sample's tone table and gray mix (lut_tap) BEFORE the blend.
+template <int DT, bool PHOTO = false, typename... Photo>
 __global__ void __launch_bounds__(256) preprocess_resample_kernel(const unsigned char* __restrict__ imgs,
                                                                   const long long* __restrict__ desc,
-                                                                  uint4* __restrict__ x4, int CH, int CW) {
+                                                                  uint4* __restrict__ x4, int CH, int CW,
+                                                                  Photo... photo) {
+  static_assert(sizeof...(Photo) == (PHOTO ? 1 : 0), "the photo region is the one extra argument of a PHOTO kernel");
+  __shared__ float lut[PHOTO ? 256 : 1];
+  bool mix = false;
+  if constexpr (PHOTO) mix = load_photo(photo..., lut);
   const Desc s = load_desc(desc);
   const int sh = s.ext ? (int)(s.ext >> 32) : s.H0, sw = s.ext ? (int)(s.ext & 0xffffffffll) : s.W0;
   const int y0 = s.ext ? s.y0 : 0, x0 = s.ext ? s.x0 : 0;
@@ -182,7 +234,7 @@ __global__ void __launch_bounds__(256) preprocess_resample_kernel(const unsigned
       float fx;
       lin_tap(ox + p, sx, sw, xa, xb, fx);
       if (s.flip) { xa = sw - 1 - xa; xb = sw - 1 - xb; }
-      w[p] = resample_px<DT>(ra, rb, (size_t)xa * s.C, (size_t)xb * s.C, s.C, fx, fy);
+      w[p] = resample_px<DT, PHOTO>(ra, rb, (size_t)xa * s.C, (size_t)xb * s.C, s.C, fx, fy, lut, mix);
     }
     out[i] = make_uint4(w[0].x, w[0].y, w[1].x, w[1].y);
   }
@@ -278,6 +330,40 @@ bool crop_desc_ok(const long long* d, long long img_bytes, long long eh, long lo
   return y0 >= 0 && x0 >= 0 && y0 <= H0 - eh && x0 <= W0 - ew;
 }
 
+// the host descriptors of an unscaled crop launch: slot 7 == 1, the valid extent of the crop inside its image
+bool crop_descs_ok(const long long* desc_host, int n, long long img_bytes, int CH, int CW, int ds) {
+  for (int i = 0; i < n; ++i) {
+    const long long* d = desc_host + (size_t)i * 8;
+    const long long vh = d[1] / ds * ds < CH ? d[1] / ds * ds : CH, vw = d[2] / ds * ds < CW ? d[2] / ds * ds : CW;
+    if (d[7] != 1 || !crop_desc_ok(d, img_bytes, vh, vw)) return false;
+  }
+  return true;
+}
+
+// the host descriptors of a scaled crop launch: slot 7 == (sh << 32) | sw, a window inside its image and within a
+// factor 4 of the crop either way
+bool scaled_descs_ok(const long long* desc_host, int n, long long img_bytes, int CH, int CW) {
+  for (int i = 0; i < n; ++i) {
+    const long long* d = desc_host + (size_t)i * 8;
+    const long long sh = d[7] >> 32, sw = d[7] & 0xffffffffll;
+    if (d[7] <= 1 || sh < 1 || sw < 1 || sh > d[1] || sw > d[2] || !crop_desc_ok(d, img_bytes, sh, sw)) return false;
+    if (sh > 4ll * CH || sw > 4ll * CW || CH > 4 * sh || CW > 4 * sw) return false;
+  }
+  return true;
+}
+
+// the host copy of a photo region: every table entry finite and in [0, 255] (a NaN fails both comparisons), every
+// gray flag 0 or 1
+bool photo_rows_ok(const float* photo_host, int n) {
+  for (int i = 0; i < n; ++i) {
+    const float* row = photo_host + (size_t)i * can::PHOTO_ROW;
+    for (int u = 0; u < 256; ++u)
+      if (!(row[u] >= 0.f && row[u] <= 255.f)) return false;
+    if (row[256] != 0.f && row[256] != 1.f) return false;
+  }
+  return true;
+}
+
 }  // namespace
 
 // Images only: the ground truth of a pack arrives at 1/ds resolution already, so dens and gt must be null.
@@ -298,11 +384,7 @@ extern "C" int can_preprocess_crop(const void* imgs, long long img_bytes, const 
                                    void* stream) {
   using namespace can;
   if (!crop_args_ok(imgs, desc, desc_host, n, x4, CH, CW, ds)) return -2;
-  for (int i = 0; i < n; ++i) {
-    const long long* d = desc_host + (size_t)i * 8;
-    const long long vh = d[1] / ds * ds < CH ? d[1] / ds * ds : CH, vw = d[2] / ds * ds < CW ? d[2] / ds * ds : CW;
-    if (d[7] != 1 || !crop_desc_ok(d, img_bytes, vh, vw)) return -2;
-  }
+  if (!crop_descs_ok(desc_host, n, img_bytes, CH, CW, ds)) return -2;
   CAN_LAUNCH_DT(dt, preprocess_crop_kernel, dim3(capped_grid((long long)CH * (CW / 2), 512), n), dim3(256), 0,
                 (hipStream_t)stream, (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW, ds);
   return (int)hipGetLastError();
@@ -315,14 +397,51 @@ extern "C" int can_preprocess_crop_scaled(const void* imgs, long long img_bytes,
                                           void* stream) {
   using namespace can;
   if (!crop_args_ok(imgs, desc, desc_host, n, x4, CH, CW, ds)) return -2;
-  for (int i = 0; i < n; ++i) {
-    const long long* d = desc_host + (size_t)i * 8;
-    const long long sh = d[7] >> 32, sw = d[7] & 0xffffffffll;
-    if (d[7] <= 1 || sh < 1 || sw < 1 || sh > d[1] || sw > d[2] || !crop_desc_ok(d, img_bytes, sh, sw)) return -2;
-    if (sh > 4ll * CH || sw > 4ll * CW || CH > 4 * sh || CW > 4 * sw) return -2;
-  }
+  if (!scaled_descs_ok(desc_host, n, img_bytes, CH, CW)) return -2;
   CAN_LAUNCH_DT(dt, preprocess_resample_kernel, dim3(capped_grid((long long)CH * (CW / 2), 512), n), dim3(256), 0,
                 (hipStream_t)stream, (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW);
+  return (int)hipGetLastError();
+}
+
+namespace {
+
+template <int DT>
+void launch_photo(int scaled, dim3 grid, hipStream_t stream, const unsigned char* imgs, const long long* desc,
+                  uint4* x4, int CH, int CW, int ds, const float* photo) {
+  using namespace can;
+  if (scaled)
+    hipLaunchKernelGGL((preprocess_resample_kernel<DT, true>), grid, dim3(256), 0, stream, imgs, desc, x4, CH, CW,
+                       photo);
+  else
+    hipLaunchKernelGGL((preprocess_crop_kernel<DT, true>), grid, dim3(256), 0, stream, imgs, desc, x4, CH, CW, ds,
+                       photo);
+}
+
+}  // namespace
+
+// can_preprocess_crop (scaled == 0) or can_preprocess_crop_scaled (scaled != 0) with photometric jitter: photo, float
+// [n][260] on the device (16-byte aligned), is one row per output sample of 256 tone-table entries on the 0..255 scale,
+// the gray flag and three zeros; photo_host is the same region on the host.  Everything the plain entry refuses is
+// refused, and so are a table entry that is not finite or leaves [0, 255] and a gray flag other than 0 or 1: all of it
+// on the host copies, before the launch.
+extern "C" int can_preprocess_crop_photo(const void* imgs, long long img_bytes, const long long* desc,
+                                         const long long* desc_host, int n, void* x4, int CH, int CW, int ds, int dt,
+                                         void* stream, const float* photo, const float* photo_host, int scaled) {
+  using namespace can;
+  if (!crop_args_ok(imgs, desc, desc_host, n, x4, CH, CW, ds)) return -2;
+  if (photo == nullptr || photo_host == nullptr || ((uintptr_t)photo & 15)) return -2;
+  if (!(scaled ? scaled_descs_ok(desc_host, n, img_bytes, CH, CW) : crop_descs_ok(desc_host, n, img_bytes, CH, CW, ds)))
+    return -2;
+  if (!photo_rows_ok(photo_host, n)) return -2;
+  const dim3 grid(capped_grid((long long)CH * (CW / 2), 512), n);
+  if (dt == DT_F16)
+    launch_photo<DT_F16>(scaled, grid, (hipStream_t)stream, (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW, ds,
+                         photo);
+  else if (dt == DT_BF16)
+    launch_photo<DT_BF16>(scaled, grid, (hipStream_t)stream, (const unsigned char*)imgs, desc, (uint4*)x4, CH, CW, ds,
+                          photo);
+  else
+    return -20;
   return (int)hipGetLastError();
 }
 

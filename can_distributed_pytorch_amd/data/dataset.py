@@ -23,6 +23,9 @@ where the image is smaller than the crop (README, "Random-crop training").
 ``gt_from_heads=True`` (with ``crop``) renders every crop's ground truth from the image's head records
 (``IMG_k.heads.npy``, data/density.py:heads_table) as exact area sums instead of resampling the density map, which
 is then never opened (README, "Ground truth from heads").
+``photo_jitter=(B, C, G)`` / ``gray_prob=P`` (with ``crop``) jitter every crop's colours: brightness, contrast and gamma as
+one 256-entry tone table per crop (``photo_draw``, ``transforms.photo_table``) applied to the source bytes before the
+flip and the resample, and a random luma mix (README, "Photometric jitter").
 ``SyntheticCrowdDataset`` provides the same item contract without files
 (benchmarks, tests, smoke runs).
 """
@@ -35,8 +38,8 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from .transforms import (_axis_weights, area_factor, heads_to_gt, heads_to_gt_padded, prepare_pair,
-                         prepare_pair_scaled)
+from .transforms import (_axis_weights, apply_photo, area_factor, heads_to_gt, heads_to_gt_padded, photo_table,
+                         prepare_pair, prepare_pair_scaled)
 
 IMG_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".tif", ".tiff")
 _M64 = (1 << 64) - 1
@@ -90,6 +93,31 @@ def check_crop_scale(lo, hi):
     if not (0.0 < lo <= hi) or lo < 0.25 or hi > 4.0:
         raise ValueError(f"crop scale range must satisfy 0.25 <= lo <= hi <= 4, got {lo},{hi}")
     return lo, hi
+
+
+def photo_draw(seed: int, epoch: int, index: int, k: int, B: float, C: float, G: float, P: float):
+    """The photometric jitter of crop ``k`` of sample ``index`` in ``epoch``: (b, c, g, gray) with the brightness shift b
+    uniform on [-B, B], the contrast factor c log-uniform on [1/(1+C), 1+C], the gamma g log-uniform on [1/G, G] and
+    gray with probability P.  Four more hashes of ``crop_draw``'s chain state (slots 5..8; 1..3 are crop_draw's, 4 is
+    scale_draw's), so it is as stateless and leaves the other draws what they are."""
+    s = _draw_state(seed, epoch, index, k)
+    u5, u6, u7, u8 = ((_splitmix64(s ^ j) >> 11) / 2 ** 53 for j in (5, 6, 7, 8))
+    return float(B * (2 * u5 - 1)), float((1.0 + C) ** (2 * u6 - 1)), float(G ** (2 * u7 - 1)), bool(u8 < P)
+
+
+def check_photo(photo_jitter, gray_prob):
+    """((B, C, G), P) as floats, or ValueError: 0 <= B <= 0.5, 0 <= C <= 1, 1 <= G <= 2, 0 <= P <= 1.  No jitter is
+    (0, 0, 1), the identity table."""
+    try:
+        B, C, G = (float(v) for v in ((0.0, 0.0, 1.0) if photo_jitter is None else photo_jitter))
+    except (TypeError, ValueError):
+        raise ValueError(f"photo jitter is (B, C, G), got {photo_jitter!r}")
+    P = float(gray_prob)
+    if not (0.0 <= B <= 0.5 and 0.0 <= C <= 1.0 and 1.0 <= G <= 2.0):
+        raise ValueError(f"photo jitter must satisfy 0 <= B <= 0.5, 0 <= C <= 1, 1 <= G <= 2, got {B},{C},{G}")
+    if not 0.0 <= P <= 1.0:
+        raise ValueError(f"gray probability must be in [0, 1], got {P}")
+    return (B, C, G), P
 
 
 def scaled_window(h0: int, w0: int, ch: int, cw: int, s: float):
@@ -198,7 +226,7 @@ def imread(path: str) -> np.ndarray:
 class CrowdDataset(Dataset):
     def __init__(self, img_root: str, gt_dmap_root: str, gt_downsample: int = 1, phase: str = "train",
                  seed: Optional[int] = None, raw: bool = False, crop=None, crops_per_image: int = 1,
-                 crop_scale=None, gt_from_heads: bool = False):
+                 crop_scale=None, gt_from_heads: bool = False, photo_jitter=None, gray_prob: float = 0.0):
         self.img_root = img_root
         self.gt_dmap_root = gt_dmap_root
         self.gt_downsample = max(1, int(gt_downsample))
@@ -234,6 +262,15 @@ class CrowdDataset(Dataset):
         if gt_from_heads and crop is None:
             raise ValueError("gt_from_heads needs crop=(ch, cw): it renders the ground truth of crop windows")
         self.gt_from_heads = bool(gt_from_heads) and self.crop is not None
+        # photo_jitter=(B, C, G) / gray_prob=P: every crop's source bytes go through its own tone table and, with
+        # probability P, the luma mix (photo_draw); either one switches it on
+        self.photo = None
+        if photo_jitter is not None or gray_prob:
+            if crop is None:
+                raise ValueError("photo_jitter / gray_prob need crop=(ch, cw): they jitter the crops' colours")
+            bcg, p = check_photo(photo_jitter, gray_prob)
+            if self.crop is not None:
+                self.photo = bcg + (p,)
 
     def __len__(self):
         return self.n_samples
@@ -288,7 +325,9 @@ class CrowdDataset(Dataset):
         of (y0, x0, flip, sh, sw)): the GPU cuts the windows (ops/preprocess.py), the ground truths are made here from
         the memory-mapped map.  gt_from_heads: the same windows; raw=False renders each ground truth with heads_to_gt /
         heads_to_gt_padded, raw=True returns the image's head records [N, 4] in place of the K ground truths (the GPU
-        renders them); no density map is opened."""
+        renders them); no density map is opened.  With photo_jitter / gray_prob: raw=False takes apply_photo of the
+        window's bytes (a float image, which prepare_pair[_scaled] keep) in place of the window; raw=True items gain a
+        fourth element, _photo_rows' float32 [K, 257], and the GPU applies the tables."""
         d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
         h0, w0 = img.shape[:2]
         scaled = self.crop_scale is not None
@@ -299,6 +338,7 @@ class CrowdDataset(Dataset):
             raise ValueError(f"{name}: density map {tuple(dmap.shape)} differs from its image {(h0, w0)}: a crop "
                              "takes the same window of both")
         ims, gts, rows = [], [], []
+        photo = self._photo_rows(epoch, index)
         for k in range(K):
             if scaled:
                 wh, ww = scaled_window(h0, w0, ch, cw, scale_draw(self.seed, epoch, index, k, *self.crop_scale))
@@ -307,6 +347,8 @@ class CrowdDataset(Dataset):
             y0, x0, fl = crop_draw(self.seed, epoch, index, k, h0 - wh + 1, w0 - ww + 1)
             im, dm = img[y0:y0 + wh, x0:x0 + ww], dmap[y0:y0 + wh, x0:x0 + ww]
             rows.append([y0, x0, int(fl)] + ([wh, ww] if scaled else []))
+            if photo is not None and not self.raw:
+                im = apply_photo(_as_uint8(im), photo[k, :256], bool(photo[k, 256]))
             if self.raw:
                 gt = density_to_gt_scaled(dm, ch, cw, d, fl) if scaled else density_to_gt(dm, wh, ww, d, fl)
             else:
@@ -315,14 +357,28 @@ class CrowdDataset(Dataset):
             gts.append(_pad_to(gt, ch // d, cw // d))
         gts = torch.from_numpy(np.stack(gts))
         if self.raw:
-            return torch.from_numpy(_as_uint8(img)), gts, torch.tensor(rows, dtype=torch.int64)
+            return (torch.from_numpy(_as_uint8(img)), gts, torch.tensor(rows, dtype=torch.int64)) + \
+                (() if photo is None else (torch.from_numpy(photo),))
         return torch.from_numpy(np.stack(ims)), gts
+
+    def _photo_rows(self, epoch: int, index: int):
+        """float32 [K, 257], crop k's tone table (photo_table of its photo_draw) and gray flag 0.0 / 1.0; None with the
+        feature off."""
+        if self.photo is None:
+            return None
+        out = np.empty((self.crops_per_image, 257), dtype=np.float32)
+        for k in range(self.crops_per_image):
+            b, c, g, gray = photo_draw(self.seed, epoch, index, k, *self.photo)
+            out[k, :256] = photo_table(b, c, g)
+            out[k, 256] = float(gray)
+        return out
 
     def _crop_item_heads(self, img: np.ndarray, heads: np.ndarray, epoch: int, index: int, scaled: bool):
         """_crop_item with the ground truth from head records: the windows and flips are the same draws."""
         d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
         h0, w0 = img.shape[:2]
         ims, gts, rows = [], [], []
+        photo = self._photo_rows(epoch, index)
         for k in range(K):
             if scaled:
                 wh, ww = scaled_window(h0, w0, ch, cw, scale_draw(self.seed, epoch, index, k, *self.crop_scale))
@@ -333,12 +389,15 @@ class CrowdDataset(Dataset):
             if self.raw:
                 continue
             im, zero = img[y0:y0 + wh, x0:x0 + ww], np.zeros((wh, ww), dtype=np.float32)
+            if photo is not None:
+                im = apply_photo(_as_uint8(im), photo[k, :256], bool(photo[k, 256]))
             im, _ = prepare_pair_scaled(im, zero, ch, cw, d, fl) if scaled else prepare_pair(im, zero, d, fl)
             ims.append(_pad_to(im, ch, cw))
             gts.append(heads_to_gt(heads, h0, w0, (y0, x0, wh, ww), ch, cw, d, fl) if scaled else
                        heads_to_gt_padded(heads, h0, w0, y0, x0, ch, cw, d, fl))
         if self.raw:
-            return torch.from_numpy(_as_uint8(img)), torch.from_numpy(heads), torch.tensor(rows, dtype=torch.int64)
+            return (torch.from_numpy(_as_uint8(img)), torch.from_numpy(heads), torch.tensor(rows, dtype=torch.int64)) + \
+                (() if photo is None else (torch.from_numpy(photo),))
         return torch.from_numpy(np.stack(ims)), torch.from_numpy(np.stack(gts))
 
 

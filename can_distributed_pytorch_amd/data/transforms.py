@@ -63,6 +63,38 @@ def gray_to_rgb(img: np.ndarray) -> np.ndarray:
     return img
 
 
+GRAY_MIX = np.array([0.299, 0.587, 0.114], dtype=np.float32)        # luma weights of (r, g, b), float32 as on the GPU
+
+
+def photo_table(b: float, c: float, g: float) -> np.ndarray:
+    """The tone table float32 [256] of a photometric draw (brightness shift b, contrast factor c about mid-gray, gamma
+    g), on the 0..255 scale: t = (u/255)^g, t = clip(c (t - 0.5) + 0.5 + b, 0, 1), table[u] = float32(255 t), in
+    float64.  The GPU kernel sees only this table, so both paths share it bit for bit; photo_table(0, 1, 1) is
+    arange(256) exactly."""
+    t = (np.arange(256, dtype=np.float64) / 255.0) ** float(g)
+    t = np.minimum(1.0, np.maximum(0.0, float(c) * (t - 0.5) + 0.5 + float(b)))
+    return (255.0 * t).astype(np.float32)
+
+
+def apply_photo(img_u8: np.ndarray, table: np.ndarray, gray: bool) -> np.ndarray:
+    """The photometric jitter of a uint8 image [H, W] / [H, W, 1 | 3 | 4] -> float64 [H, W, 3] in [0, 1]: every byte
+    through the tone table, with ``gray`` a colour pixel's three channels replaced by their luma (GRAY_MIX, summed in
+    float64 in the kernel's order; a 1-channel image is left alone, alpha is dropped), then / 255.  prepare_pair and
+    prepare_pair_scaled keep a float image as it is, so the jitter precedes the flip and the resample."""
+    if img_u8.dtype != np.uint8:
+        raise ValueError(f"apply_photo takes the decoded uint8 image, got {img_u8.dtype}")
+    table = np.asarray(table)
+    if table.shape != (256,) or table.dtype != np.float32:
+        raise ValueError("the tone table is float32 [256]")
+    one = img_u8.ndim == 2 or img_u8.shape[2] == 1
+    t = gray_to_rgb(table.astype(np.float64)[img_u8])
+    if gray and not one:
+        w = GRAY_MIX.astype(np.float64)
+        y = w[2] * t[..., 2] + (w[1] * t[..., 1] + w[0] * t[..., 0])
+        t = np.stack([y, y, y], axis=2)
+    return t / 255.0
+
+
 def normalize_chw(img_hwc: np.ndarray) -> np.ndarray:
     chw = img_hwc.transpose(2, 0, 1).astype(np.float32)
     return (chw - IMAGENET_MEAN[:, None, None]) / IMAGENET_STD[:, None, None]

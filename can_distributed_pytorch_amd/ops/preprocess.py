@@ -16,8 +16,10 @@ resize launch's kernel resamples it to the crop.  With ``gt_from_heads=True``
 a cropped pack carries the images' head records instead of ground-truth
 values and a second launch on the same stream (csrc/density.hip,
 gt_from_heads_kernel) renders the ground truth region of the buffer from
-them.  A pack of any kind goes through one collate loop, ``_unpack`` and
-``_launch``.
+them.  With ``photo=True`` a cropped pack ends with one tone-table row per
+output sample and the image launch goes through the photo entry (README,
+"Photometric jitter").  A pack of any kind goes through one collate loop,
+``_unpack`` and ``_launch``.
 """
 from __future__ import annotations
 
@@ -81,12 +83,23 @@ class PackedCollate:
     (uint8 image, head records [N,4] fp32, windows).  The ground truth region is zero (the GPU renders it in place),
     and behind the descriptors follow the int64 ranges [n, 2] = (first head, head count) of every output sample -- the
     K crops of an image share one range -- and the head table [sum N, 4] fp32, both 16-byte aligned.  The meta tuple
-    has eight fields, (..., images, scaled 0 / 1, heads in the table), a length no other kind has."""
+    has eight fields, (..., images, scaled 0 / 1, heads in the table), a length no other kind has.
+    photo=True (with crop, any of the four kinds): for CrowdDataset(..., photo_jitter= / gray_prob=) items, which carry
+    a fourth element, float32 [K, 257] (tone table, gray flag).  Everything above is packed as without it, byte for
+    byte, and behind it (16-byte aligned) follows the photo region float32 [n, 260], one row per output sample: the 256
+    table entries, the gray flag, three zeros.  The meta tuple has nine fields, a length no other kind has:
+    (n, Ho, Wo, gt_offset, desc_offset, images, kind, heads, photo_offset), kind the index 1 / 2 into KINDS and heads -1
+    without a head table."""
 
-    def __init__(self, downsample: int = 8, crop=None, crop_scale=False, gt_from_heads=False):
+    PHOTO_ROW = 260                               # floats per row of the photo region (csrc/preprocess.hip)
+
+    def __init__(self, downsample: int = 8, crop=None, crop_scale=False, gt_from_heads=False, photo=False):
         self.ds = downsample
         self.crop_scale = bool(crop_scale)
         self.gt_from_heads = bool(gt_from_heads)
+        self.photo = bool(photo)
+        if self.photo and crop is None:
+            raise ValueError("photo needs crop=(ch, cw)")
         if self.crop_scale and crop is None:
             raise ValueError("crop_scale needs crop=(ch, cw)")
         if self.gt_from_heads and crop is None:
@@ -117,10 +130,23 @@ class PackedCollate:
             raise ValueError("scaled windows must have extents 1 <= sh, sw < 2^31")
         return [(fl, y0, x0, (sh << 32) | sw) for y0, x0, fl, sh, sw in third.tolist()]
 
+    def _photo_region(self, photos, n):
+        """float32 [n, PHOTO_ROW] from the items' [K, 257] rows: table, gray flag, three zeros."""
+        for ph in photos:
+            if not torch.is_tensor(ph) or ph.dtype != torch.float32 or ph.dim() != 2 or ph.shape[1] != 257:
+                raise ValueError("photo items must carry float32 [K, 257] rows (tone table, gray flag)")
+        rows = torch.cat(photos)
+        if rows.shape[0] != n:
+            raise ValueError(f"photo rows: {rows.shape[0]} for {n} output samples")
+        region = torch.zeros(n, self.PHOTO_ROW)
+        region[:, :257] = rows
+        return region
+
     @staticmethod
     def _fill(imgs, ioff, gt, desc, tail=None):
         """One buffer: the images back to back | the ground truth at goff | the descriptors at doff (16-byte aligned),
-        then ``tail`` (the ranges and the head table of a heads pack, a multiple of 16 bytes after 64 n)."""
+        then ``tail`` (the ranges and the head table of a heads pack, the photo region of a photo pack: multiples of
+        16 bytes after 64 n)."""
         goff = -(-ioff // 16) * 16
         doff = -(-(goff + 4 * gt.numel()) // 16) * 16
         buf = torch.empty(doff + 8 * desc.numel() + (0 if tail is None else tail.numel()), dtype=torch.uint8)
@@ -136,7 +162,10 @@ class PackedCollate:
         return buf, goff, doff
 
     def __call__(self, batch: List):
-        imgs, gts, thirds = zip(*batch)            # the third field: a flip (uncropped) or the [K, 3 / 5] windows
+        if any(len(item) != 3 + self.photo for item in batch):
+            raise ValueError("a photo collate takes the 4-element items of a dataset with photo_jitter / gray_prob, "
+                             "every other collate 3-element items")
+        imgs, gts, thirds = list(zip(*batch))[:3]  # the third field: a flip (uncropped) or the [K, 3 / 5] windows
         if self.crop is None:
             ho, wo = (imgs[0].shape[0] // self.ds) * self.ds, (imgs[0].shape[1] // self.ds) * self.ds
         else:
@@ -152,14 +181,21 @@ class PackedCollate:
                 ranges += [[hoff, g.shape[0]]] * len(wins)
                 hoff += g.shape[0]
         desc = torch.tensor(rows, dtype=torch.int64)
+        tails = []
         if self.gt_from_heads:
             gt = torch.zeros(len(rows), 1, ho // self.ds, wo // self.ds)
-            tail = torch.cat([torch.tensor(ranges, dtype=torch.int64).reshape(-1).view(torch.uint8),
-                              torch.cat(gts).contiguous().reshape(-1).view(torch.uint8)])
-            buf, goff, doff = self._fill(imgs, ioff, gt, desc, tail)
+            tails = [torch.tensor(ranges, dtype=torch.int64).reshape(-1).view(torch.uint8),
+                     torch.cat(gts).contiguous().reshape(-1).view(torch.uint8)]
+        else:
+            gt = (torch.stack(gts) if self.crop is None else torch.cat(gts)).float().contiguous()
+        if self.photo:
+            tails.append(self._photo_region([item[3] for item in batch], len(rows)).reshape(-1).view(torch.uint8))
+        buf, goff, doff = self._fill(imgs, ioff, gt, desc, torch.cat(tails) if tails else None)
+        if self.photo:
+            return buf, (len(rows), ho, wo, goff, doff, len(imgs), 1 + int(self.crop_scale),
+                         hoff if self.gt_from_heads else -1, buf.numel() - 4 * self.PHOTO_ROW * len(rows))
+        if self.gt_from_heads:
             return buf, (len(rows), ho, wo, goff, doff, len(imgs), int(self.crop_scale), hoff)
-        gt = (torch.stack(gts) if self.crop is None else torch.cat(gts)).float().contiguous()
-        buf, goff, doff = self._fill(imgs, ioff, gt, desc)
         kind = () if self.crop is None else (len(imgs), 1) if self.crop_scale else (len(imgs),)
         return buf, (len(rows), ho, wo, goff, doff) + kind
 
@@ -171,17 +207,25 @@ def _unpack(packed):
     """(buf, (n, Ho, Wo, gt_offset, desc_offset), kind) of a PackedCollate output, kind one of KINDS: a cropped
     pack's meta tuple carries a sixth field (its number of images) and n counts output samples, one descriptor each;
     a scaled pack's carries a seventh, 1.  A heads pack's meta tuple has eight fields (images, scaled 0 / 1, heads):
-    its kind is "crop+heads" or "crop_scaled+heads", and its buffer ends with the ranges and the head table."""
+    its kind is "crop+heads" or "crop_scaled+heads", and its buffer ends with the ranges and the head table.  A photo
+    pack's has nine (images, kind 1 / 2, heads or -1, photo_offset): its kind ends with "+photo", and its buffer with
+    the photo region [n, 260] fp32 at photo_offset."""
     buf, meta = packed
     n, ho, wo, goff, doff = meta[:5]
-    heads = len(meta) == 8
+    photo = len(meta) == 9
+    heads = len(meta) == 8 or (photo and meta[7] >= 0)
     meta_ok = len(meta) in (5, 6) or (len(meta) == 7 and meta[6] == 1) or \
-        (heads and meta[6] in (0, 1) and meta[7] >= 0)
+        (len(meta) == 8 and meta[6] in (0, 1) and meta[7] >= 0) or (photo and meta[6] in (1, 2) and meta[7] >= -1)
     size = doff + 64 * n + ((16 * n + 16 * meta[7]) if heads and meta_ok else 0)
+    if photo and meta_ok:
+        meta_ok = meta[8] == size                 # right behind what the pack holds without it (a multiple of 16)
+        size += 4 * PackedCollate.PHOTO_ROW * n
     buf_ok = buf.dtype == torch.uint8 and buf.dim() == 1 and buf.numel() == size
     if not (meta_ok and buf_ok) or goff % 16 or doff % 16:
         raise ValueError("packed batch: one uint8 buffer (images | fp32 ground truth | int64 descriptors"
-                         " [| int64 head ranges | fp32 head records])")
+                         " [| int64 head ranges | fp32 head records] [| fp32 photo rows])")
+    if photo:
+        return buf, (n, ho, wo, goff, doff), KINDS[meta[6]] + ("+heads" if heads else "") + "+photo"
     if heads:
         return buf, (n, ho, wo, goff, doff), KINDS[1 + meta[6]] + "+heads"
     return buf, (n, ho, wo, goff, doff), KINDS[len(meta) - 5]
@@ -189,24 +233,29 @@ def _unpack(packed):
 
 def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device):
     """The one launch of a pack of any kind: d, the device copy of buf -> (x4, gt), gt a view of d.  The crop entries
-    check the host descriptors (in buf) before they launch."""
+    check the host descriptors (in buf) before they launch, the photo entry the host photo rows as well."""
     hd, wd = ho // downsample, wo // downsample
     gt = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
     desc = d[doff:doff + 64 * n].view(torch.int64).view(n, 8)
     x4 = torch.empty(n, ho, wo, 4, dtype=dtype, device=device)
     tail = (ho, wo, downsample, dt_code(dtype), _ext.stream_ptr(device))
-    kind, _, heads = kind.partition("+")
+    kind, *flags = kind.split("+")
+    heads, photo = "heads" in flags, "photo" in flags
+    poff = buf.numel() - (4 * PackedCollate.PHOTO_ROW * n if photo else 0)      # the photo region ends the buffer
     if heads:
         # checked on the host copies before EITHER launch (a refused pack launches nothing); the render itself is
         # issued right after the image launch, on the same stream
         roff, hoff = doff + 64 * n, doff + 80 * n
-        nh = (buf.numel() - hoff) // 16
+        nh = (poff - hoff) // 16
         rc = C.gt_from_heads_check(buf.data_ptr() + hoff, nh, buf.data_ptr() + roff, buf.data_ptr() + doff, n, ho, wo,
                                    downsample)
         if rc:
             raise RuntimeError(f"gt_from_heads refused the pack (code {rc})")
     if kind == "batch":
         C.preprocess_batch(d.data_ptr(), 0, desc.data_ptr(), n, x4.data_ptr(), 0, *tail)
+    elif photo:
+        C.preprocess_crop_photo(d.data_ptr(), goff, desc.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(), *tail,
+                                d.data_ptr() + poff, buf.data_ptr() + poff, int(kind == "crop_scaled"))
     else:
         getattr(C, "preprocess_" + kind)(d.data_ptr(), goff, desc.data_ptr(), buf.data_ptr() + doff, n, x4.data_ptr(),
                                          *tail)

@@ -93,6 +93,23 @@ def crop_scale(v):
     return lo, hi
 
 
+def photo_jitter(v):
+    try:
+        b, c, g = (float(x) for x in str(v).split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--photo-jitter expects B,C,G, got {v!r}")
+    if not (0.0 <= b <= 0.5 and 0.0 <= c <= 1.0 and 1.0 <= g <= 2.0):
+        raise argparse.ArgumentTypeError(f"--photo-jitter must satisfy 0 <= B <= 0.5, 0 <= C <= 1, 1 <= G <= 2, got {v!r}")
+    return b, c, g
+
+
+def gray_prob(v):
+    p = float(v)
+    if not 0.0 <= p <= 1.0:
+        raise argparse.ArgumentTypeError(f"--gray-prob must be in [0, 1], got {v!r}")
+    return p
+
+
 def crop_count(v):
     n = int(v)
     if n < 1:
@@ -109,6 +126,11 @@ class _Parser(argparse.ArgumentParser):
             self.error("--crop-scale rescales the windows of --crop-size; give --crop-size as well")
         if ns.gt_from_heads and ns.crop_size is None:
             self.error("--gt-from-heads renders the ground truth of the crops of --crop-size; give --crop-size as well")
+        for flag, value in (("--photo-jitter", ns.photo_jitter), ("--gray-prob", ns.gray_prob)):
+            if value is not None and ns.synthetic:
+                self.error(f"{flag} jitters the crops of decoded dataset images; it cannot be combined with --synthetic")
+            if value is not None and ns.crop_size is None:
+                self.error(f"{flag} jitters the colours of the crops of --crop-size; give --crop-size as well")
         return ns
 
 
@@ -206,6 +228,15 @@ def build_parser():
                         "k_nearest_gaussian_kernel.py <root> --heads) as exact area sums of the density map, on the GPU "
                         "with --gpu-preprocess, instead of point-sampling the map: a cell holds its window's density "
                         "mass at any scale.  Default: off")
+    p.add_argument("--photo-jitter", type=photo_jitter, default=None, metavar="B,C,G",
+                   help="with --crop-size: every crop draws a brightness shift uniform on [-B, B] (0 <= B <= 0.5, of the "
+                        "0..1 range), a contrast factor log-uniform on [1/(1+C), 1+C] about mid-gray (0 <= C <= 1) and a "
+                        "gamma log-uniform on [1/G, G] (1 <= G <= 2), e.g. 0.2,0.3,1.5; they act on the source pixels as "
+                        "one 256-entry tone table per crop, inside the crop launch with --gpu-preprocess.  Training "
+                        "crops only.  Default: off")
+    p.add_argument("--gray-prob", type=gray_prob, default=None, metavar="P",
+                   help="with --crop-size: every crop is turned gray (luma 0.299 R + 0.587 G + 0.114 B in all three "
+                        "channels, after the tone table of --photo-jitter) with this probability.  Default: off")
     p.add_argument("--log-every", type=int, default=20,
                    help="steps between the training records of --log-jsonl (each reads the loss back: a host sync)")
     return p
@@ -222,11 +253,12 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
     collate = PackedCollate() if raw else None
     crop = args.crop_size
     train_collate, eval_batch = collate, args.batch_size
+    photo = args.photo_jitter is not None or args.gray_prob is not None
     if crop is not None:
         # every training sample is a crop of one size; test images stay whole and of mixed size: batch 1
         from can_distributed_pytorch_amd.data.dataset import crop_collate
         train_collate = PackedCollate(crop=crop, crop_scale=args.crop_scale is not None,
-                                      gt_from_heads=args.gt_from_heads) if raw else crop_collate
+                                      gt_from_heads=args.gt_from_heads, photo=photo) if raw else crop_collate
         eval_batch = 1
     if args.synthetic:
         h, w = (int(v) for v in args.synthetic.lower().split("x"))
@@ -237,7 +269,9 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
         train_ds = CrowdDataset(os.path.join(r, "train_data", "images"), os.path.join(r, "train_data", "ground_truth"),
                                 gt_downsample=8, phase="train", seed=args.seed, raw=raw, crop=crop,
                                 crops_per_image=args.crops_per_image if crop is not None else 1,
-                                crop_scale=args.crop_scale, gt_from_heads=args.gt_from_heads)
+                                crop_scale=args.crop_scale, gt_from_heads=args.gt_from_heads,
+                                **(dict(photo_jitter=args.photo_jitter or (0.0, 0.0, 1.0),
+                                        gray_prob=args.gray_prob or 0.0) if photo else {}))
         test_ds = CrowdDataset(os.path.join(r, "test_data", "images"), os.path.join(r, "test_data", "ground_truth"),
                                gt_downsample=8, phase="test", raw=raw)
     train_sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed)
@@ -404,6 +438,8 @@ def main(args):
                             eval_batch_size=test_loader.batch_size) if args.crop_size is not None else {}),
                     **(dict(crop_scale=list(args.crop_scale)) if args.crop_scale is not None else {}),
                     **(dict(gt_from_heads=True) if args.gt_from_heads else {}),
+                    **(dict(photo_jitter=list(args.photo_jitter)) if args.photo_jitter is not None else {}),
+                    **(dict(gray_prob=args.gray_prob) if args.gray_prob is not None else {}),
                     **(dict(ema_decay=args.ema_decay) if ema_on else {}))
             if use_wandb:
                 wandb_log(loss=mean_loss, mae=mean_mae, lr=lr_now)
