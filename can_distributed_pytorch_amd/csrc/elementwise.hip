@@ -495,12 +495,15 @@ __device__ __forceinline__ float4 ema4(float w, float4 p, float4 e) {
   return make_float4(ema1(w, p.x, e.x), ema1(w, p.y, e.y), ema1(w, p.z, e.z), ema1(w, p.w, e.w));
 }
 
-// The new optimizers' packs are the 16-bit rounding of the fp32 master as stored: without the barrier the compiler
-// folds the update's last fma into the conversion (v_fma_mixlo_f16: the exact fma result rounded once, to fp16), which
-// differs from a re-pack of the stored master in rare double-rounding cases.  (OPT_NONE / OPT_SGD: code unchanged.)
+// Every optimizer's packs are the 16-bit rounding of the fp32 master as stored, on every store path: resume,
+// swap_weights and refresh_packs re-pack from the stored masters and must reproduce them.  Without the barrier the
+// compiler folds the update's last fma into the conversion (v_fma_mixlo_f16: the exact fma result rounded once, to
+// fp16), which differs from a re-pack of the stored master in rare double-rounding cases (the master lands on an fp16
+// midpoint after an update below half an fp32 ulp; 5.5e-5 of N(0, 0.3) weights per SGD step at lr = 3e-3).
+// tests/test_gpu_optpack_exact.py pins it with directed cases.  (OPT_NONE packs a loaded value: nothing to fold.)
 template <int OPT>
 __device__ __forceinline__ float as_stored(float x) {
-  if constexpr (OPT >= OPT_SGD_WD) asm volatile("" : "+v"(x));
+  if constexpr (OPT != OPT_NONE) asm volatile("" : "+v"(x));
   return x;
 }
 
@@ -672,30 +675,16 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
       t[c][r] = f2h<DT>(v.x); t[c][r + 1] = f2h<DT>(v.y); t[c][r + 2] = f2h<DT>(v.z); t[c][r + 3] = f2h<DT>(v.w);
     }
   } else {
-    // OPT_SGD packs a ragged tile from the update's fma folded into the 16-bit conversion (see as_stored) and a v4
-    // tile from the master as stored.  With EMA a whole tile can land here only because the EMA arena is off float4
-    // alignment: it still packs from the master as stored (STORED), so the packs do not depend on where the EMA
-    // arena lies.
-#define CAN_RAGGED_TILE(STORED)                                                             \
-    for (int i = threadIdx.x; i < cos_ * row; i += 256) {                                   \
-      const int c = i / row, r = i - c * row;                                               \
-      float* pw = w + ((size_t)(co0 + c) * Ci + ci0) * taps + r;                            \
-      float v = pw[0];                                                                      \
-      if constexpr (OPT == OPT_SWAP) v = swap1(pw);                                         \
-      else if constexpr (OPT != OPT_NONE) v = step1(pw, v, pw[sa.goff], pw[sa.boff]);       \
-      if constexpr (STORED) asm volatile("" : "+v"(v));                                     \
-      t[c][r] = f2h<DT>(as_stored<OPT>(v));                                                 \
+    // ragged tiles, and whole tiles of a misaligned slot or arena: element-wise, packed from the master as stored like
+    // every other path (as_stored), so the packs depend neither on the tile shape nor on where an arena lies
+    for (int i = threadIdx.x; i < cos_ * row; i += 256) {
+      const int c = i / row, r = i - c * row;
+      float* pw = w + ((size_t)(co0 + c) * Ci + ci0) * taps + r;
+      float v = pw[0];
+      if constexpr (OPT == OPT_SWAP) v = swap1(pw);
+      else if constexpr (OPT != OPT_NONE) v = step1(pw, v, pw[sa.goff], pw[sa.boff]);
+      t[c][r] = f2h<DT>(as_stored<OPT>(v));
     }
-    if constexpr (EMA && OPT == OPT_SGD) {
-      if (v4n) {
-        CAN_RAGGED_TILE(true)
-      } else {
-        CAN_RAGGED_TILE(false)
-      }
-    } else {
-      CAN_RAGGED_TILE(false)
-    }
-#undef CAN_RAGGED_TILE
   }
   __syncthreads();
   if (first) {
