@@ -153,6 +153,12 @@ int can_synth_render(const float* dens, const float* noise, float* dmax, void* x
 int can_preprocess_density(const float* d, int H0, int W0, int flip, float* out, int Ho, int Wo, float mult,
                            void* stream);
 
+// CUs of the current device, asked once (0: no device), and a 4-KiB page of zeros on it (nullptr: allocation failed):
+// one of each for every kernel family (defined in conv_igemm.hip)
+int can_device_cus();
+const void* can_zero_page();
+
+// views of the launch plan (conv_plan.h plan_conv) under the process's dispatch config
 int can_conv_plan(int H, int W, int Cin, int Cout, int ksize, int dil, int epi);
 int can_splitk_plan(int N, int H, int W, int Cin, int Cout, int ksize, int dil, int epi);
 int can_splitk_dirty();

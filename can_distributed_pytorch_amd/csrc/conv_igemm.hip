@@ -28,9 +28,12 @@
 //     to the other LDS buffer after them (one barrier per K step);
 //   * 1-D grid with a bijective XCD-aware remap so that the channel tiles
 //     sharing one pixel tile (and its halo) run on the same XCD / L2.
+#include "api.h"
 #include "common.h"
+#include "conv_plan.h"
 #include "fastdiv.h"
 #include <stdlib.h>
+#include <type_traits>
 #include <vector>
 
 namespace can {
@@ -63,14 +66,7 @@ struct ConvArgs {
 // in one K-concatenated GEMM and needs the fp32 accumulator, not its 16-bit rounding.
 // EPI_CTXF / EPI_CTXB (LDS-DMA v2 kernel, 256 x 256 tiles, 1x1): the context module as ONE GEMM each way,
 // see "Linearised context module" below.
-enum { EPI_BIAS_RELU = 0, EPI_MASK = 1, EPI_NONE = 2, EPI_BIAS = 3, EPI_SIGMOID = 4, EPI_POOLBWD = 5,
-       EPI_POOLFWD = 6, EPI_F32 = 7, EPI_CTXF = 8, EPI_CTXB = 9,
-       // EPI_MASK whose ReLU mask comes as SIGN BITS (internal: the host API passes EPI_MASK + a bit tensor).
-       // Sign bits of a 16-bit activation map [M][C]: byte m * (C / 8) + c / 8, bit c % 8 = (value > 0) on the
-       // stored 16-bit pattern (pos_bits).  Written by the producing conv's forward epilogue (1/16 of the map's
-       // bytes), they replace the data gradient's 2-byte-per-element mask read: conv1_2's data gradient reads
-       // 50 MB instead of conv1_1's 805 MB output at batch 8 x 768 x 1024, conv2_2's 25 instead of 403 MB
-       EPI_MASKB = 10 };
+// The EPI_* enum (and the sign-bit layout of EPI_MASKB) is in conv_plan.h.
 
 // sign bits of 8 consecutive 16-bit values (two per 32-bit word, low half first): bit k = value k > 0
 __device__ __forceinline__ unsigned sign_bits8(unsigned w0, unsigned w1, unsigned w2, unsigned w3) {
@@ -298,15 +294,8 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
 }
 
 template <int DT, int LOAD, int EPI>
-static int dispatch_tiles(const ConvArgs& a, int tile_cfg, hipStream_t s) {
-  // tile_cfg: 0 = auto, 1 = 128ch x 128pix, 2 = 64ch x 256pix, 3 = 128ch x 256pix, 4 = 256ch x 128pix
-  int cfg = tile_cfg;
-  if (cfg == 0) {
-    if (a.Cout % 128 != 0) cfg = 2;
-    else if (a.Cout % 256 == 0 && a.M >= 65536) cfg = 4;
-    else cfg = 1;
-  }
-  switch (cfg) {
+static int launch_generic(const ConvArgs& a, int cfg, hipStream_t s) {
+  switch (cfg) {                                   // the generic tiles of kTileCfgs
     case 1: return launch_conv<DT, 2, 2, LOAD, EPI>(a, s);
     case 2: return launch_conv<DT, 1, 4, LOAD, EPI>(a, s);
     case 3: return launch_conv<DT, 2, 4, LOAD, EPI>(a, s);
@@ -1366,29 +1355,7 @@ __global__ void __launch_bounds__(64 * WC * WP, 1) conv_glds2_kernel(ConvArgs2 a
   }
 }
 
-static int device_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    CAN_HIP_CHECK(hipGetDevice(&dev));
-    CAN_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  return ncu;
-}
-
-// Split-K on small grids: a row-ring (2-row tiles) or LDS-DMA v2 launch whose grid fills at most half the CUs (the
-// 1/8-resolution 512-channel layers at batch 1: 48-96 tiles; a 480 x 640 image's LDS-DMA layers: 19-75 tiles for 256
-// CUs) splits its 64-channel input chunks over KS = min(chunks, CUs / tiles) blocks per tile (<= one block per CU),
-// joined by splitk_fixup.  Scratch: fp32 partials of <= CUs blocks (256 KB each for 256-channel tiles) and one
-// arrival counter per tile, allocated once and zeroed (the last part resets its counter).  Dispatch splitk = 0: off.
-constexpr size_t SK_PART_BYTES = (size_t)64 << 20;
-constexpr int SK_COUNTERS = 4096;
-static int splitk_ks(int tiles, int Cin, int TR) {
-  if (!g_dispatch.splitk || TR != 2 || tiles < 1) return 1;
-  const int ncu = device_cus();
-  if (2 * tiles > ncu || tiles > SK_COUNTERS) return 1;
-  return std::max(1, std::min(Cin / 64, ncu / tiles));
-}
+// Split-K scratch (the split itself is planned by conv_plan.h splitk_ks).
 // One scratch slot per (device, launch stream): launches on one stream are ordered, so the partials and arrival
 // counters of one slot are never shared by two running split-K grids, whichever streams issue convs (the executor's
 // compute stream, the graph-capture stream, an evaluation stream, a second device).  A slot is allocated and zeroed
@@ -1402,7 +1369,11 @@ static bool splitk_slot_alloc(SkSlot& sl) {
   void *p = nullptr, *c = nullptr;
   if (hipMalloc(&p, SK_PART_BYTES) != hipSuccess) return false;
   if (hipMalloc(&c, SK_COUNTERS * sizeof(unsigned)) != hipSuccess) { (void)hipFree(p); return false; }
-  if (hipMemset(c, 0, SK_COUNTERS * sizeof(unsigned)) != hipSuccess) return false;
+  if (hipMemset(c, 0, SK_COUNTERS * sizeof(unsigned)) != hipSuccess) {
+    (void)hipFree(p);
+    (void)hipFree(c);
+    return false;
+  }
   sl.part = p;
   sl.cnt = (unsigned*)c;
   return true;
@@ -1437,7 +1408,7 @@ static bool splitk_scratch(hipStream_t s, float** part, unsigned** cnt) {
 }
 
 template <int DT, int WC, int WP, int PW, int EPI>
-static int launch_glds2(const ConvArgs2& a, hipStream_t s, int nb = 1) {
+static int launch_glds2(const ConvArgs2& a, hipStream_t s, int ks = 1, int nb = 1) {
   constexpr int TC = 64 * WC, TP = 64 * PW * WP;
   size_t lds = 2 * (size_t)(TC + TP) * 128;
   ConvArgs2 b = a;
@@ -1455,15 +1426,8 @@ static int launch_glds2(const ConvArgs2& a, hipStream_t s, int nb = 1) {
     attr_lds = lds;
   }
   const int nct = a.Cout / TC, npt = (a.M + TP - 1) / TP;
-  // split-K on a small grid (splitk_ks): single launches, not the context epilogues
-  b.rr_ks = 1;
-  if (nb == 1 && EPI != EPI_CTXF && EPI != EPI_CTXB) {
-    b.rr_ks = splitk_ks(nct * npt, a.Cin, 2);
-    if (b.rr_ks > 1) {
-      if ((size_t)nct * npt * b.rr_ks * (64 * WC * WP) * (256 * PW) > SK_PART_BYTES) b.rr_ks = 1;
-      else if (!splitk_scratch(s, &b.sk_part, &b.sk_cnt)) return -10;
-    }
-  }
+  b.rr_ks = ks;                                    // split-K on a small grid (planned: conv_plan.h splitk_ks)
+  if (ks > 1 && !splitk_scratch(s, &b.sk_part, &b.sk_cnt)) return -10;
   hipLaunchKernelGGL(kfn, dim3(nct * npt * b.rr_ks, nb), dim3(64 * WC * WP), lds, s, b);
   return (int)hipGetLastError();
 }
@@ -1734,49 +1698,8 @@ __global__ void __launch_bounds__(512, 1) conv_rring_kernel(ConvArgs2 a) {
   glds_epilogue<DT, WC, WP, PW, EPI, TR, RG>(a, acc, ct, pt, wc, wp, fr, fq);
 }
 
-// column-block utilisation of the row ring on a ragged width: W / (ceil(W / 128) * 128) >= 0.6 (W = 240, 480,
-// 960: 94 %; 80, 160: 62.5 %); below it (W = 72, 135: 53-56 %) the per-tap LDS-DMA kernel, whose pixel tiles run
-// across rows, wastes less.  (Round 6 lowered it from 0.7: 480 x 640's 1/4- and 1/8-resolution maps, 160 and 80
-// columns, ran the LDS-DMA kernel on 150-228-block grids at 10-20 % of the MFMA rate; on the row ring the batch-1
-// step is 5.7 % faster, 345.9 / 346.1 -> 365.8 / 365.3 img/s, profiles/r6/ab_rring_width_480x640.jsonl.)
-// A ragged width must be a multiple of 8: the row DMA's validity is then uniform per 8-pixel piece (see issue_rows)
-static bool rring_width_ok(int W) {
-  if (W % 128 == 0) return true;
-  const int tx = (W + 127) / 128;
-  return W % 8 == 0 && W >= 64 && 10 * W >= 6 * 128 * tx;
-}
-// pixel tiles of the row ring: N * ceil(H / TR) * ceil(W / 128) (ragged last tile row / column block masked)
-static int rr_np(int H, int W, int M, int TR) {
-  return (M / (H * W)) * ((H + TR - 1) / TR) * ((W + 127) / 128);
-}
-// the row-ring kernel applies: 3x3, dilation 1 / 2, a width the column blocks cover well (rring_width_ok); Cout % 256
-// == 0 (cfg 27, 2-row tiles), Cout % 128 (cfg 29) or Cout == 64 (cfg 28, 4-row tiles); 0 = not applicable
-static int rring_cfg(int H, int W, int Cin, int Cout, int ksize, int dil, int epi) {
-  if (ksize != 3 || (dil != 1 && dil != 2) || !rring_width_ok(W) || Cin % 64 || epi == EPI_POOLFWD ||
-      epi == EPI_SIGMOID || epi == EPI_CTXF || epi == EPI_CTXB)
-    return 0;
-  if (Cout % 256 == 0) return 27;
-  // cfg 29 (128 x (2 x 128), the wave tile of cfg 22): dispatch rring128 = 1 (default) for the dilation-1 cfg-22
-  // layers (K > 1152: conv3_1's data gradient 0.270 -> 0.253 ms), = 2 also for the cfg-25 ones (128 x 512 tiles,
-  // K <= 1152: conv2_2 +2 %), = 3 also dilation 2 (backend.8 forward +10 %); 0 = off (profiles/r3/ab_rring128.txt)
-  const int m128 = g_dispatch.rring128;
-  if (Cout % 128 == 0 && Cout % 256 != 0 && m128 >= ((9 * Cin > 1152) ? 1 : 2) && (dil == 1 || m128 >= 3))
-    return 29;
-  // cfg 28 (dispatch rring64 = 0: off): conv2_1's data gradient 0.435 -> 0.347 ms isolated, step 487.3 -> 489.9
-  // img/s (profiles/r3/ab_dma_order.txt)
-  if (Cout == 64) return 28;
-  return 0;
-}
-// dispatch rring: 0 = off, 1 = dilation-1 layers, 2 (default) = every dilation.  With the after-group DMA placement
-// (CANNET_DMA_ORDER_RR = 1) the dilation-2 layers gain too: step 497.0 -> 501.3 img/s (profiles/r3/ab_rring128.txt).
-// Before that placement, per layer at batch 8 x 768 x 1024
-// (profiles/r3/ab_rring.txt) -2..-6 % vs cfg 21 with the rows issued 3 stages ahead (issued 2 ahead with a full
-// DMA drain per stage: dilation 1 -1..-4 %, dilation 2 +1..+7 %); the step: off 482.6, dilation 1 485.4, every
-// dilation 484.9 img/s (medians of 4 interleaved rounds)
-static int rring_mode() { return g_dispatch.rring; }
-
 template <int DT, int EPI, int TC, int TR, int LEAD, int D, bool RG>
-static int launch_rring_rg(const ConvArgs2& a, hipStream_t s) {
+static int launch_rring_rg(const ConvArgs2& a, const ConvPlan& p, hipStream_t s) {
   auto kfn = conv_rring_kernel<DT, EPI, D, LEAD, TC, TR, RG>;
   static bool attr = false;
   if (!attr) {
@@ -1786,39 +1709,27 @@ static int launch_rring_rg(const ConvArgs2& a, hipStream_t s) {
   ConvArgs2 b = a;
   b.rr_tx = (a.W + 127) / 128;
   b.rr_ty = (a.H + TR - 1) / TR;
-  b.rr_np = rr_np(a.H, a.W, a.M, TR);
-  const int tiles = (a.Cout / TC) * b.rr_np;
-  b.rr_ks = splitk_ks(tiles, a.Cin, TR);      // (the pool epilogue too: same tiles, same split as conv_igemm)
-  if (b.rr_ks > 1) {
-    // partial bytes per (tile, part): 512 threads x 4 x 4 PW f32x4 = TC / 256 x 256 KB
-    if ((size_t)tiles * b.rr_ks * (size_t)TC * 1024 > SK_PART_BYTES) b.rr_ks = 1;
-    else if (!splitk_scratch(s, &b.sk_part, &b.sk_cnt)) return -10;
-  }
-  hipLaunchKernelGGL(kfn, dim3(tiles * b.rr_ks), dim3(512), rr_lds(TC, TR), s, b);
+  b.rr_np = p.npt;
+  b.rr_ks = p.ks;                             // (the pool epilogue too: same tiles, same split as conv_igemm)
+  if (p.ks > 1 && !splitk_scratch(s, &b.sk_part, &b.sk_cnt)) return -10;
+  hipLaunchKernelGGL(kfn, dim3(p.tiles * p.ks), dim3(512), rr_lds(TC, TR), s, b);
   return (int)hipGetLastError();
 }
-template <int DT, int EPI, int TC, int TR, int LEAD, int D>
-static int launch_rring_one(const ConvArgs2& a, hipStream_t s) {
-  if (a.W % 128 == 0 && a.H % TR == 0) return launch_rring_rg<DT, EPI, TC, TR, LEAD, D, false>(a, s);
-  return launch_rring_rg<DT, EPI, TC, TR, LEAD, D, true>(a, s);
-}
-
-template <int DT, int EPI>
-static int launch_rring(const ConvArgs2& a, hipStream_t s, int cfg) {
-  if constexpr (EPI == EPI_POOLFWD || EPI == EPI_SIGMOID || EPI == EPI_CTXF || EPI == EPI_CTXB) {
-    return -16;
+// the aligned (W % 128 == 0, H % TR == 0) or the ragged instantiation; rows are issued LEAD stages ahead of their
+// first tap (2-row tiles: 3, per layer 0.4 % ahead of 4, profiles/r3/ab_rring.txt)
+template <int DT, int EPI, int TC, int TR, int LEAD>
+static int launch_rring(const ConvArgs2& a, const ConvPlan& p, hipStream_t s) {
+  if constexpr (EPI == EPI_POOLFWD) {              // dilation 1, whole tiles only (plan_pool)
+    if constexpr (TR == 2) return launch_rring_rg<DT, EPI, TC, TR, LEAD, 1, false>(a, p, s);
+    else return -16;
   } else {
-    if (rring_cfg(a.H, a.W, a.Cin, a.Cout, a.ksize, a.dil, EPI) != cfg) return -16;
-    if (cfg == 28)
-      return a.dil == 1 ? launch_rring_one<DT, EPI, 64, 4, 2, 1>(a, s) : launch_rring_one<DT, EPI, 64, 4, 2, 2>(a, s);
-    if (cfg == 29)
-      return a.dil == 1 ? launch_rring_one<DT, EPI, 128, 2, 3, 1>(a, s) : launch_rring_one<DT, EPI, 128, 2, 3, 2>(a, s);
-    // rows are issued 3 stages ahead of their first tap (per layer 0.4 % ahead of 4, profiles/r3/ab_rring.txt)
-    if (a.dil == 1) return launch_rring_one<DT, EPI, 256, 2, 3, 1>(a, s);
-    return launch_rring_one<DT, EPI, 256, 2, 3, 2>(a, s);
+    if (a.dil == 1)
+      return p.ragged ? launch_rring_rg<DT, EPI, TC, TR, LEAD, 1, true>(a, p, s)
+                      : launch_rring_rg<DT, EPI, TC, TR, LEAD, 1, false>(a, p, s);
+    return p.ragged ? launch_rring_rg<DT, EPI, TC, TR, LEAD, 2, true>(a, p, s)
+                    : launch_rring_rg<DT, EPI, TC, TR, LEAD, 2, false>(a, p, s);
   }
 }
-
 // ===========================================================================
 // Halo-tiled 3x3 / dilation-1 conv for Cin = 64 (conv1_2 fwd + dgrad, conv2_1
 // fwd: the 768x1024 / 384x512 layers).  The generic kernel streams the
@@ -2427,20 +2338,15 @@ static int launch_ws64(const HaloConvArgs& a, hipStream_t s) {
   // 2 halo buffers of 6 rows x 72 pixel slots (+ W1G: 12 shifted image planes of 6 x 72 16-bit words)
   constexpr size_t lds = 2 * (size_t)(6 * 9) * 1024 + (W1G ? 12 * 6 * 72 * 2 + 13 * 256 + 8 * 192 * 16 : 0);
   auto kfn = conv_ws64_kernel<DT, EPI, W1G, MB>;
-  static int ncu = 0;
-  if (!ncu) {
+  static bool attr = false;
+  if (!attr) {
     CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int dev = 0;
-    CAN_HIP_CHECK(hipGetDevice(&dev));
-    CAN_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    attr = true;
   }
-  const int grid = ws64_grid(a.N * a.tiles_y * a.tiles_x, ncu);   // every block gets a non-empty run
+  const int grid = ws64_grid(a.N * a.tiles_y * a.tiles_x, can_device_cus());   // every block gets a non-empty run
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, s, a);
   return (int)hipGetLastError();
 }
-
-// ws64 (weight-stationary) instead of the halo kernel for Cin = Cout = 64 (dispatch ws64 = 0: halo kernel)
-static bool use_ws64() { return g_dispatch.ws64 != 0; }
 
 // ===========================================================================
 // First layer (conv1_1: 3 -> 64, 3x3, input NHWC4 bf16 = 8 B per pixel).
@@ -2626,76 +2532,57 @@ static int launch_glds(const ConvArgs2& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-// default LDS-DMA tile config: v2 (pipelined); 128 x 512 tiles measured faster for K <= 1152
-static int glds_default_cfg(int Cin, int Cout, int ksize) {
-  const int ktot = ksize * ksize * Cin;
-  return (Cout % 256 == 0) ? 21 : (Cout % 128 == 0) ? (ktot <= 1152 ? 25 : 22) : 23;
-}
-static int glds_cfg_tp(int cfg) {   // pixels per tile of a v2 config
-  return (cfg == 21 || cfg == 22) ? 256 : (cfg == 23 || cfg == 25) ? 512 : 0;
-}
-// rows of the bias-partial matrix an LDS-DMA config writes: pixel tiles x waves along the pixels (0: none); the
-// row ring's pixel tiles are per-image row groups x column blocks (rr_np)
-static int glds_bpart_rows(int cfg, int M, int H, int W) {
-  int tp = 0, wp = 0;
-  switch (cfg) {
-    case 27: return rr_np(H, W, M, 2) * 2;     // 256 ch x (2 x 128) px, 4 x 2 waves
-    case 29: return rr_np(H, W, M, 2) * 4;     // 128 x (2 x 128), 2 x 4
-    case 28: return rr_np(H, W, M, 4) * 8;     // 64 x (4 x 128), 1 x 8
-    case 11: case 21: tp = 256; wp = 2; break;   // 256 ch x 256 px, 4 x 2 waves
-    case 12: case 22: tp = 256; wp = 4; break;   // 128 x 256, 2 x 4
-    case 13: case 23: tp = 512; wp = 8; break;   // 64 x 512, 1 x 8
-    case 25: tp = 512; wp = 4; break;            // 128 x 512, 2 x 4 (2 fragments per wave)
-    default: return 0;
-  }
-  return ((M + tp - 1) / tp) * wp;
-}
-
+// The LDS-DMA / row-ring launch of a plan: config -> template arguments (the WC, WP, PW / TC, TR of kTileCfgs), for
+// the epilogues each family is built for.
 template <int DT, int EPI>
-static int dispatch_glds(const ConvArgs2& a, int tile_cfg, hipStream_t s, int nb = 1) {
-  int cfg = tile_cfg;
-  if (cfg == 0) cfg = glds_default_cfg(a.Cin, a.Cout, a.ksize);
-  if constexpr (EPI == EPI_POOLFWD) {
-    const int tp = glds_cfg_tp(cfg);
-    if (tp == 0 || (a.H & 1) || a.W % (tp / 2) || a.yp == nullptr) return -12;
-  }
-  if constexpr (EPI == EPI_POOLBWD) {
-    if (a.pcodes == nullptr) return -14;
-  }
-  switch (cfg) {
-    case 11: if (a.Cout % 256 || EPI == EPI_POOLFWD || nb > 1) return -8; return launch_glds<DT, 4, 2, 2, EPI>(a, s);
-    case 12: if (a.Cout % 128 || EPI == EPI_POOLFWD || nb > 1) return -8; return launch_glds<DT, 2, 4, 1, EPI>(a, s);
-    case 13: if (EPI == EPI_POOLFWD || nb > 1) return -8; return launch_glds<DT, 1, 8, 1, EPI>(a, s);
-    case 21: if (a.Cout % 256) return -8; return launch_glds2<DT, 4, 2, 2, EPI>(a, s, nb);
-    case 22: if (a.Cout % 128) return -8; return launch_glds2<DT, 2, 4, 1, EPI>(a, s, nb);
-    case 23: return launch_glds2<DT, 1, 8, 1, EPI>(a, s, nb);
-    case 25: if (a.Cout % 128) return -8; return launch_glds2<DT, 2, 4, 2, EPI>(a, s, nb);   // 128 x 512, 160 KB LDS
-    case 27: case 28: case 29: if (nb > 1) return -8; return launch_rring<DT, EPI>(a, s, cfg);    // row ring
+static int launch_tile(const ConvArgs2& a, const ConvPlan& p, hipStream_t s, int nb = 1) {
+  constexpr bool ctx = EPI == EPI_CTXF || EPI == EPI_CTXB;
+  constexpr bool v1 = !ctx && EPI != EPI_MASKB;    // v1 tiles; the row ring, which has no sigmoid epilogue either
+  constexpr bool ring = v1 && EPI != EPI_SIGMOID;
+  switch (p.cfg) {
+    case 11: if constexpr (v1) return launch_glds<DT, 4, 2, 2, EPI>(a, s); break;
+    case 12: if constexpr (v1) return launch_glds<DT, 2, 4, 1, EPI>(a, s); break;
+    case 13: if constexpr (v1) return launch_glds<DT, 1, 8, 1, EPI>(a, s); break;
+    case 21: return launch_glds2<DT, 4, 2, 2, EPI>(a, s, p.ks, nb);
+    case 22: if constexpr (!ctx) return launch_glds2<DT, 2, 4, 1, EPI>(a, s, p.ks, nb); break;
+    case 23: if constexpr (!ctx) return launch_glds2<DT, 1, 8, 1, EPI>(a, s, p.ks, nb); break;
+    case 24: if constexpr (ctx) return launch_glds2<DT, 2, 2, 1, EPI>(a, s); break;
+    case 25: if constexpr (!ctx) return launch_glds2<DT, 2, 4, 2, EPI>(a, s, p.ks, nb); break;
+    case 27: if constexpr (ring) return launch_rring<DT, EPI, 256, 2, 3>(a, p, s); break;
+    case 28: if constexpr (ring) return launch_rring<DT, EPI, 64, 4, 2>(a, p, s); break;
+    case 29: if constexpr (ring) return launch_rring<DT, EPI, 128, 2, 3>(a, p, s); break;
   }
   return -9;
 }
 
-// EPI_MASKB (the ReLU mask as sign bits) runs on the v2 LDS-DMA tiles only (the data-gradient configs of conv2_2-like
-// layers: 128 x 512 for K <= 1152 and the other v2 tiles); other configs return -17
-static bool maskb_cfg_ok(int cfg) { return cfg == 21 || cfg == 22 || cfg == 23 || cfg == 25; }
-template <int DT>
-static int dispatch_glds_maskb(const ConvArgs2& a, int cfg, hipStream_t s) {
-  switch (cfg) {
-    case 21: if (a.Cout % 256) return -8; return launch_glds2<DT, 4, 2, 2, EPI_MASKB>(a, s);
-    case 22: if (a.Cout % 128) return -8; return launch_glds2<DT, 2, 4, 1, EPI_MASKB>(a, s);
-    case 23: return launch_glds2<DT, 1, 8, 1, EPI_MASKB>(a, s);
-    case 25: if (a.Cout % 128) return -8; return launch_glds2<DT, 2, 4, 2, EPI_MASKB>(a, s);
-  }
-  return -17;
+// f(std::integral_constant<int, E>) for the E of the list that equals the run-time epilogue (-6: none does)
+template <int... E, class F>
+static int with_epi(int epi, F&& f) {
+  int rc = -6;
+  (void)((epi == E && ((rc = f(std::integral_constant<int, E>{})), true)) || ...);
+  return rc;
 }
 
-static const bf16_t* conv_zero_page() {
-  static void* z = nullptr;
-  if (!z) {
-    if (hipMalloc(&z, 4096) != hipSuccess) return nullptr;
-    if (hipMemset(z, 0, 4096) != hipSuccess) return nullptr;
-  }
-  return (const bf16_t*)z;
+// kernel arguments of the LDS-DMA / row-ring kernels (zero == nullptr: no zero page, -10) and of the halo-tiled ones
+// (4 x tcol output tiles); the epilogue-specific fields are the caller's
+static ConvArgs2 conv_args2(const void* x, const void* w, const float* bias, const void* mask, void* y,
+                            const ConvQuery& q) {
+  ConvArgs2 b;
+  b.x = (const bf16_t*)x; b.w = (const bf16_t*)w; b.bias = bias; b.mask = (const bf16_t*)mask; b.y = (bf16_t*)y;
+  b.zero = (const bf16_t*)can_zero_page();
+  b.H = q.H; b.W = q.W; b.Cin = q.Cin; b.Cout = q.Cout; b.ksize = q.ksize; b.dil = q.dil; b.M = q.N * q.H * q.W;
+  b.fdW = make_fastdiv((uint32_t)q.W); b.fdH = make_fastdiv((uint32_t)q.H);
+  b.wv = valid_width(q);
+  return b;
+}
+static HaloConvArgs halo_args(const void* x, const void* w, const float* bias, const void* mask, void* y,
+                              const ConvQuery& q, int tcol) {
+  HaloConvArgs h;
+  h.x = (const bf16_t*)x; h.w = (const bf16_t*)w; h.bias = bias; h.mask = (const bf16_t*)mask; h.y = (bf16_t*)y;
+  h.zero = (const bf16_t*)can_zero_page();
+  h.N = q.N; h.H = q.H; h.W = q.W; h.tiles_x = (q.W + tcol - 1) / tcol; h.tiles_y = (q.H + 3) / 4;
+  h.wv = valid_width(q);
+  return h;
 }
 
 template <int DT>
@@ -2704,129 +2591,55 @@ static int conv_igemm_impl(const void* x, const void* w, const float* bias, cons
                            int epi, int first, int tile_cfg, void* stream, float* bpart, int bpart_cap,
                            int* bpart_rows, const void* mbits_in, void* mbits_out, int wv) {
   if (bpart_rows) *bpart_rows = 0;
-  if (wv <= 0 || wv > W) wv = W;                   // valid width of a width-padded map (W = row pitch)
-  const bool padded = wv < W && (epi == EPI_BIAS_RELU || epi == EPI_BIAS);
-  if (epi != EPI_MASK && epi != EPI_POOLBWD) bpart = nullptr;
-  if (mbits_in != nullptr && epi != EPI_MASK) return -17;
-  // sign-bit outputs: the first layer and the Cin = 64 -> 128 halo kernel (conv1_1, conv2_1), ReLU epilogue
-  if (mbits_out != nullptr &&
-      !(epi == EPI_BIAS_RELU && ksize == 3 && dil == 1 && Cin == (first ? 4 : 64) &&
-        (first ? (Cout == 64 && (tile_cfg == 0 || tile_cfg == 32)) : (Cout == 128 && (tile_cfg == 0 || tile_cfg == 31)))))
-    return -18;
-  ConvArgs a;
-  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.bias = bias; a.mask = (const bf16_t*)mask;
-  a.y = (bf16_t*)y; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = ksize; a.dil = dil;
-  a.M = N * H * W;
-  if (Cout % 64 != 0) return -2;
-  if (!first && Cin % 64 != 0) return -3;
-  if (first && (Cin != 4 || ksize != 3)) return -4;
+  const ConvQuery q{ENTRY_IGEMM, N, H, W, Cin, Cout, ksize, dil, epi, tile_cfg, wv, first, 1, mbits_in != nullptr,
+                    mbits_out != nullptr, bpart != nullptr, bpart_cap};
+  const ConvPlan p = plan_conv(q, g_dispatch, can_device_cus());
+  if (p.err) return p.err;
+  if (bpart_rows) *bpart_rows = p.bpart_rows;
+  if (p.bpart_rows == 0) bpart = nullptr;
   hipStream_t s = (hipStream_t)stream;
-#define CAN_EPI_CASE(L, E) \
-  if (epi == E) return dispatch_tiles<DT, L, E>(a, tile_cfg, s);
-  const bool auto_halo = tile_cfg == 0;
-  if (first) {
-    if ((tile_cfg == 32 || auto_halo) && Cout == 64 && epi == EPI_BIAS_RELU) {
-      HaloConvArgs h;
-      h.x = a.x; h.w = a.w; h.bias = a.bias; h.mask = nullptr; h.y = a.y; h.zero = nullptr;
-      h.mbo = (unsigned char*)mbits_out;
-      h.N = N; h.H = H; h.W = W; h.tiles_x = (W + 127) / 128; h.tiles_y = (H + 3) / 4;
-      h.wv = wv;
-      const int ntile = N * h.tiles_y * h.tiles_x;
-      // persistent: two blocks per CU, the next tile's halo loaded under the current stores (0.272 -> 0.189 ms)
-      static int ncu = 0;
-      if (!ncu) {
-        int dev = 0;
-        CAN_HIP_CHECK(hipGetDevice(&dev));
-        CAN_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-      }
-      hipLaunchKernelGGL((conv_first_halo_kernel<DT, true, true>), dim3(std::min(ntile, 2 * ncu)), dim3(512), 0, s, h);
-      return (int)hipGetLastError();
-    }
-    if (padded) return -19;                        // the generic first-layer kernel takes no padding
-    CAN_EPI_CASE(LOAD_FIRST, EPI_BIAS_RELU)
-    return -5;
+  const TileCfg& t = *find_tile_cfg(p.cfg);
+  if (t.fam == FAM_GENERIC) {
+    const ConvArgs a{(const bf16_t*)x, (const bf16_t*)w, bias, (const bf16_t*)mask, (bf16_t*)y,
+                     N, H, W, Cin, Cout, ksize, dil, N * H * W};
+    if (first) return launch_generic<DT, LOAD_FIRST, EPI_BIAS_RELU>(a, p.cfg, s);
+    return with_epi<EPI_BIAS_RELU, EPI_MASK, EPI_NONE, EPI_BIAS, EPI_SIGMOID>(epi, [&](auto e) {
+      return launch_generic<DT, LOAD_GENERIC, decltype(e)::value>(a, p.cfg, s);
+    });
   }
-  if (auto_halo && Cin == 64 && ksize == 3 && dil == 1 && (Cout == 64 || Cout == 128) && epi != EPI_SIGMOID &&
-      epi != EPI_POOLBWD && epi != EPI_F32 && mbits_in == nullptr)
-    tile_cfg = 31;
-  if (tile_cfg == 31) {
-    // halo-tiled Cin = 64 kernel (explicit; see conv_halo64_kernel)
-    if (Cin != 64 || ksize != 3 || dil != 1 || (Cout != 64 && Cout != 128)) return -11;
-    if (mbits_in != nullptr) return -17;
-    HaloConvArgs h;
-    h.x = a.x; h.w = a.w; h.bias = a.bias; h.mask = a.mask; h.y = a.y; h.zero = conv_zero_page();
+  if (t.fam == FAM_FIRST || t.fam == FAM_HALO || t.fam == FAM_WS64) {
+    const int tcol = tile_cols(t, Cout);
+    HaloConvArgs h = halo_args(x, w, bias, first ? nullptr : mask, y, q, tcol);
     if (!h.zero) return -10;
     h.mbo = (unsigned char*)mbits_out;
-    h.wv = wv;
-    // Cout = 64: 64-column tiles, two blocks per CU
-    const bool narrow = Cout == 64;
-    h.N = N; h.H = H; h.W = W; h.tiles_x = narrow ? (W + 63) / 64 : (W + 127) / 128; h.tiles_y = (H + 3) / 4;
-    if (bpart != nullptr && epi == EPI_MASK) {
-      const int rows_per_tile = (Cout == 128) ? 4 : narrow ? 4 : 8;   // NW * 64 / CO
-      const long long rows = (long long)N * h.tiles_y * h.tiles_x * rows_per_tile;
-      if (rows <= bpart_cap) { h.bpart = bpart; if (bpart_rows) *bpart_rows = (int)rows; }
+    h.bpart = bpart;
+    if (t.fam == FAM_FIRST) {
+      // persistent: two blocks per CU, the next tile's halo loaded under the current stores (0.272 -> 0.189 ms)
+      hipLaunchKernelGGL((conv_first_halo_kernel<DT, true, true>), dim3(std::min(p.tiles, 2 * can_device_cus())),
+                         dim3(512), 0, s, h);
+      return (int)hipGetLastError();
     }
-    if (narrow && h.bpart == nullptr && use_ws64()) {
-      switch (epi) {
-        case EPI_BIAS_RELU: return launch_ws64<DT, EPI_BIAS_RELU>(h, s);
-        case EPI_MASK: return launch_ws64<DT, EPI_MASK>(h, s);
-        case EPI_NONE: return launch_ws64<DT, EPI_NONE>(h, s);
-        case EPI_BIAS: return launch_ws64<DT, EPI_BIAS>(h, s);
-      }
-    }
-#define CAN_HALO_CASE(E) \
-    if (epi == E) return (Cout == 128) ? launch_halo64<DT, 128, E, 128>(h, s) \
-                         : narrow ? launch_halo64<DT, 64, E, 64>(h, s) : launch_halo64<DT, 64, E, 128>(h, s);
-    CAN_HALO_CASE(EPI_BIAS_RELU)
-    CAN_HALO_CASE(EPI_MASK)
-    CAN_HALO_CASE(EPI_NONE)
-    CAN_HALO_CASE(EPI_BIAS)
-#undef CAN_HALO_CASE
-    return -6;
+    return with_epi<EPI_BIAS_RELU, EPI_MASK, EPI_NONE, EPI_BIAS>(epi, [&](auto e) {
+      constexpr int E = decltype(e)::value;
+      return t.fam == FAM_WS64 ? launch_ws64<DT, E>(h, s)
+             : (Cout == 128)   ? launch_halo64<DT, 128, E, 128>(h, s)
+             : tcol == 64      ? launch_halo64<DT, 64, E, 64>(h, s) : launch_halo64<DT, 64, E, 128>(h, s);
+    });
   }
-  if (tile_cfg == 0 || tile_cfg >= 10) {
-    if (H < 2 || W < 2) return -7;
-    ConvArgs2 b;
-    b.x = a.x; b.w = a.w; b.bias = a.bias; b.mask = a.mask; b.y = a.y; b.zero = conv_zero_page();
-    if (!b.zero) return -10;
-    if (epi == EPI_POOLBWD) { b.mask = nullptr; b.pcodes = (const uint32_t*)mask; }   // mask = max-pool codes
-    b.H = H; b.W = W; b.Cin = Cin; b.Cout = Cout; b.ksize = ksize; b.dil = dil; b.M = a.M;
-    if (tile_cfg == 0 && rring_mode() >= dil) tile_cfg = rring_cfg(H, W, Cin, Cout, ksize, dil, epi);
-    if (mbits_in != nullptr) {
-      if (tile_cfg == 0) tile_cfg = glds_default_cfg(Cin, Cout, ksize);
-      if (!maskb_cfg_ok(tile_cfg)) return -17;
-    }
-    if (bpart != nullptr) {
-      const int rows = glds_bpart_rows(tile_cfg ? tile_cfg : glds_default_cfg(Cin, Cout, ksize), a.M, H, W);
-      if (rows > 0 && rows <= bpart_cap) { b.bpart = bpart; if (bpart_rows) *bpart_rows = rows; }
-    }
-    b.fdW = make_fastdiv((uint32_t)W); b.fdH = make_fastdiv((uint32_t)H);
-    b.wv = wv;
-    if (mbits_in != nullptr) {
-      b.mask = nullptr;
-      b.mbits = (const unsigned char*)mbits_in;
-      return dispatch_glds_maskb<DT>(b, tile_cfg, s);
-    }
-    switch (epi) {
-      case EPI_BIAS_RELU: return dispatch_glds<DT, EPI_BIAS_RELU>(b, tile_cfg, s);
-      case EPI_MASK: return dispatch_glds<DT, EPI_MASK>(b, tile_cfg, s);
-      case EPI_NONE: return dispatch_glds<DT, EPI_NONE>(b, tile_cfg, s);
-      case EPI_BIAS: return dispatch_glds<DT, EPI_BIAS>(b, tile_cfg, s);
-      case EPI_SIGMOID: return dispatch_glds<DT, EPI_SIGMOID>(b, tile_cfg, s);
-      case EPI_POOLBWD: return dispatch_glds<DT, EPI_POOLBWD>(b, tile_cfg, s);
-      case EPI_F32: return dispatch_glds<DT, EPI_F32>(b, tile_cfg, s);
-    }
-    return -6;
+  ConvArgs2 b = conv_args2(x, w, bias, mask, y, q);
+  if (!b.zero) return -10;
+  b.bpart = bpart;
+  if (epi == EPI_POOLBWD) {                        // mask = max-pool codes
+    if (mask == nullptr) return -14;
+    b.mask = nullptr; b.pcodes = (const uint32_t*)mask;
   }
-  if (mbits_in != nullptr) return -17;
-  if (padded) return -19;                          // the generic kernel takes no padding
-  CAN_EPI_CASE(LOAD_GENERIC, EPI_BIAS_RELU)
-  CAN_EPI_CASE(LOAD_GENERIC, EPI_MASK)
-  CAN_EPI_CASE(LOAD_GENERIC, EPI_NONE)
-  CAN_EPI_CASE(LOAD_GENERIC, EPI_BIAS)
-  CAN_EPI_CASE(LOAD_GENERIC, EPI_SIGMOID)
-#undef CAN_EPI_CASE
-  return -6;
+  if (mbits_in != nullptr) {
+    b.mask = nullptr; b.mbits = (const unsigned char*)mbits_in;
+    return launch_tile<DT, EPI_MASKB>(b, p, s);
+  }
+  return with_epi<EPI_BIAS_RELU, EPI_MASK, EPI_NONE, EPI_BIAS, EPI_SIGMOID, EPI_POOLBWD, EPI_F32>(epi, [&](auto e) {
+    return launch_tile<DT, decltype(e)::value>(b, p, s);
+  });
 }
 
 // nb independent convs of one shape in ONE launch of the v2 kernel (grid.y = item): the context module's four
@@ -2836,22 +2649,15 @@ template <int DT>
 static int conv_igemm_batched_impl(const void* x, const void* w, const float* bias, void* y, int nb, long long xbs,
                                    long long wbs, long long ybs, int N, int H, int W, int Cin, int Cout, int ksize,
                                    int dil, int epi, int tile_cfg, hipStream_t s) {
-  if (nb < 1 || nb > 65535 || Cin % 64 || Cout % 64 || H < 2 || W < 2) return -2;
-  if (tile_cfg != 0 && tile_cfg < 20) return -8;
-  ConvArgs2 b;
-  b.x = (const bf16_t*)x; b.w = (const bf16_t*)w; b.bias = bias; b.mask = nullptr; b.y = (bf16_t*)y;
-  b.zero = conv_zero_page();
+  const ConvQuery q{ENTRY_BATCHED, N, H, W, Cin, Cout, ksize, dil, epi, tile_cfg, 0, 0, nb};
+  const ConvPlan p = plan_conv(q, g_dispatch, can_device_cus());
+  if (p.err) return p.err;
+  ConvArgs2 b = conv_args2(x, w, bias, nullptr, y, q);
   if (!b.zero) return -10;
-  b.H = H; b.W = W; b.Cin = Cin; b.Cout = Cout; b.ksize = ksize; b.dil = dil; b.M = N * H * W;
-  b.fdW = make_fastdiv((uint32_t)W); b.fdH = make_fastdiv((uint32_t)H);
   b.xbs = xbs; b.wbs = wbs; b.ybs = ybs;
-  const int cfg = tile_cfg ? tile_cfg : glds_default_cfg(Cin, Cout, ksize);   // always a v2 config
-  switch (epi) {
-    case EPI_NONE: return dispatch_glds<DT, EPI_NONE>(b, cfg, s, nb);
-    case EPI_SIGMOID: return dispatch_glds<DT, EPI_SIGMOID>(b, cfg, s, nb);
-    case EPI_BIAS_RELU: return dispatch_glds<DT, EPI_BIAS_RELU>(b, cfg, s, nb);
-  }
-  return -6;
+  return with_epi<EPI_NONE, EPI_SIGMOID, EPI_BIAS_RELU>(epi, [&](auto e) {
+    return launch_tile<DT, decltype(e)::value>(b, p, s, nb);
+  });
 }
 
 // Linearised context module GEMMs (see "Linearised context module").  fwd = 1: x = fv [M][C], w = W2cat
@@ -2860,76 +2666,40 @@ static int conv_igemm_batched_impl(const void* x, const void* w, const float* bi
 template <int DT>
 static int conv_ctx_impl(int fwd, const void* x, const void* w, const float* tab0, const float* tab1,
                          const void* fv, void* cat, void* y, int N, int H, int W, int C, hipStream_t s, int wv) {
-  if (C % 256 || W < 64 || H < 1) return -2;       // 256 x 256 tiles; <= 5 image rows per 256-pixel tile
-  if (wv <= 0 || wv > W) wv = W;                   // valid width of a width-padded map (W = row pitch)
-  ConvArgs2 b;
-  b.x = (const bf16_t*)x; b.w = (const bf16_t*)w; b.bias = nullptr; b.y = (bf16_t*)y;
-  b.zero = conv_zero_page();
+  const ConvQuery q{ENTRY_CTX, N, H, W, fwd ? C : 4 * C, fwd ? 4 * C : C, 1, 1, fwd ? EPI_CTXF : EPI_CTXB, 0, wv};
+  const ConvPlan p = plan_conv(q, g_dispatch, can_device_cus());
+  if (p.err) return p.err;
+  ConvArgs2 b = conv_args2(x, w, nullptr, fwd ? nullptr : fv, y, q);
   if (!b.zero) return -10;
-  b.H = H; b.W = W; b.ksize = 1; b.dil = 1; b.M = N * H * W;
-  b.Cin = fwd ? C : 4 * C;
-  b.Cout = fwd ? 4 * C : C;
-  b.fdW = make_fastdiv((uint32_t)W); b.fdH = make_fastdiv((uint32_t)H);
-  b.wv = wv; b.fdWv = make_fastdiv((uint32_t)wv);
+  b.fdWv = make_fastdiv((uint32_t)b.wv);
   b.ctab0 = tab0; b.ctab1 = tab1; b.cat = (bf16_t*)cat; b.cC = C;
-  // tiles: 256 x 256 (8 waves, one block per CU) or 128 x 128 (4 waves, 64 KB ring: two blocks per CU, one block's
-  // epilogue beside the other's main loop); dispatch ctx_tile_f / ctx_tile_b select
-  const int tile = fwd ? g_dispatch.ctx_tile_f : g_dispatch.ctx_tile_b;
-  if (fwd) {
-    b.mask = nullptr; b.fvp = (const bf16_t*)fv;
-    return tile == 128 ? launch_glds2<DT, 2, 2, 1, EPI_CTXF>(b, s) : launch_glds2<DT, 4, 2, 2, EPI_CTXF>(b, s);
-  }
-  b.mask = (const bf16_t*)fv;
-  return tile == 128 ? launch_glds2<DT, 2, 2, 1, EPI_CTXB>(b, s) : launch_glds2<DT, 4, 2, 2, EPI_CTXB>(b, s);
+  if (!fwd) return launch_tile<DT, EPI_CTXB>(b, p, s);
+  b.fvp = (const bf16_t*)fv;
+  return launch_tile<DT, EPI_CTXF>(b, p, s);
 }
 
 // 3x3 / 1x1 conv + bias + ReLU with the 2x2/s2 max-pool fused into the epilogue: yp = pooled output,
 // codes = its max-pool codes (what the backward needs), y = the full-resolution output (optional: nullptr
-// skips its 2-byte-per-element store).  LDS-DMA v2 kernels and conv1_2's halo kernel.
+// skips its 2-byte-per-element store).  LDS-DMA v2 kernels, the row ring and conv1_2's halo kernel.
 template <int DT>
 static int conv_pool_fwd_impl(const void* x, const void* w, const float* bias, void* y, void* yp, void* codes,
                               int N, int H, int W, int Cin, int Cout, int ksize, int dil, int tile_cfg,
                               hipStream_t s, int wv) {
-  if (Cout % 64 || Cin % 64 || H < 2 || W < 2) return -3;
-  if (wv <= 0 || wv > W) wv = W;                   // valid width of a width-padded map (W = row pitch)
-  if (wv % 2) return -19;                          // pool windows wholly inside or outside the valid columns
-  if (ksize == 3 && dil == 1 && H % 2 == 0 && W % 128 == 0 && Cin % 64 == 0 &&
-      ((tile_cfg == 0 && g_dispatch.rring_pool && Cout % 256 == 0) || (tile_cfg == 27 && Cout % 256 == 0) ||
-       (tile_cfg == 29 && Cout % 128 == 0))) {
-    // row ring with the max-pool in the epilogue: 256 x (2 x 128) tiles (Cout % 256 == 0) or 128 x (2 x 128).
-    // Default (dispatch rring_pool) only the 256-channel form: conv3_3 + pool 0.429 -> 0.384 ms; the 128-channel
-    // one loses to conv_glds2's 128 x 512 tile on conv2_2 (0.588 -> 0.639 ms), profiles/r4/ab_rring_pool.txt
-    ConvArgs2 b;
-    b.x = (const bf16_t*)x; b.w = (const bf16_t*)w; b.bias = bias; b.mask = nullptr; b.y = (bf16_t*)y;
-    b.yp = (bf16_t*)yp; b.codes = (uint32_t*)codes; b.zero = conv_zero_page();
-    if (!b.zero) return -10;
-    b.H = H; b.W = W; b.Cin = Cin; b.Cout = Cout; b.ksize = ksize; b.dil = dil; b.M = N * H * W;
-    b.fdW = make_fastdiv((uint32_t)W); b.fdH = make_fastdiv((uint32_t)H);
-    b.wv = wv;
-    const bool wide = (tile_cfg == 27) || (tile_cfg == 0 && Cout % 256 == 0);
-    return wide ? launch_rring_rg<DT, EPI_POOLFWD, 256, 2, 3, 1, false>(b, s)
-                : launch_rring_rg<DT, EPI_POOLFWD, 128, 2, 3, 1, false>(b, s);
-  }
-  if (Cin == 64 && Cout == 64 && ksize == 3 && dil == 1 && tile_cfg == 0) {
-    // conv1_2: halo-tiled kernel, 4 x 64 output tiles (full tiles only: the pool epilogue has barriers)
-    if (H % 4 || W % 64) return -13;
-    HaloConvArgs h;
-    h.x = (const bf16_t*)x; h.w = (const bf16_t*)w; h.bias = bias; h.mask = nullptr; h.y = (bf16_t*)y;
-    h.yp = (bf16_t*)yp; h.codes = (uint32_t*)codes; h.zero = conv_zero_page();
+  const ConvQuery q{ENTRY_POOL, N, H, W, Cin, Cout, ksize, dil, EPI_POOLFWD, tile_cfg, wv};
+  const ConvPlan p = plan_conv(q, g_dispatch, can_device_cus());
+  if (p.err) return p.err;
+  const int fam = find_tile_cfg(p.cfg)->fam;
+  if (fam == FAM_HALO || fam == FAM_WS64) {
+    HaloConvArgs h = halo_args(x, w, bias, nullptr, y, q, 64);
     if (!h.zero) return -10;
-    h.N = N; h.H = H; h.W = W; h.tiles_x = W / 64; h.tiles_y = H / 4;
-    h.wv = wv;
-    if (use_ws64()) return launch_ws64<DT, EPI_POOLFWD>(h, s);
-    return launch_halo64<DT, 64, EPI_POOLFWD, 64>(h, s);
+    h.yp = (bf16_t*)yp; h.codes = (uint32_t*)codes;
+    return fam == FAM_WS64 ? launch_ws64<DT, EPI_POOLFWD>(h, s) : launch_halo64<DT, 64, EPI_POOLFWD, 64>(h, s);
   }
-  ConvArgs2 b;
-  b.x = (const bf16_t*)x; b.w = (const bf16_t*)w; b.bias = bias; b.mask = nullptr; b.y = (bf16_t*)y;
-  b.yp = (bf16_t*)yp; b.codes = (uint32_t*)codes; b.zero = conv_zero_page();
+  ConvArgs2 b = conv_args2(x, w, bias, nullptr, y, q);
   if (!b.zero) return -10;
-  b.H = H; b.W = W; b.Cin = Cin; b.Cout = Cout; b.ksize = ksize; b.dil = dil; b.M = N * H * W;
-  b.fdW = make_fastdiv((uint32_t)W); b.fdH = make_fastdiv((uint32_t)H);
-  b.wv = wv;
-  return dispatch_glds<DT, EPI_POOLFWD>(b, tile_cfg, s);
+  if (fam == FAM_GLDS2 && yp == nullptr) return -12;
+  b.yp = (bf16_t*)yp; b.codes = (uint32_t*)codes;
+  return launch_tile<DT, EPI_POOLFWD>(b, p, s);
 }
 
 // conv1_2's data gradient (ws64, EPI_MASK: dX = relu-masked, mask = conv1_1's output) with conv1_1's weight
@@ -2939,17 +2709,12 @@ template <int DT>
 static int conv_ws64_dgrad_w1g_impl(const void* dy, const void* w, const void* mask, const void* img, void* y,
                                     float* w1slab, float* w1bslab, int slab_cap, int N, int H, int W, hipStream_t s,
                                     const void* mbits) {
-  HaloConvArgs h;
-  h.x = (const bf16_t*)dy; h.w = (const bf16_t*)w; h.bias = nullptr; h.mask = (const bf16_t*)mask;
-  h.mbi = (const unsigned char*)mbits;
   if (mask == nullptr && mbits == nullptr) return -17;
-  h.y = (bf16_t*)y; h.zero = conv_zero_page();
+  HaloConvArgs h = halo_args(dy, w, nullptr, mask, y, ConvQuery{ENTRY_IGEMM, N, H, W, 64, 64}, 64);
   if (!h.zero) return -10;
+  h.mbi = (const unsigned char*)mbits;
   h.img = (const bf16_t*)img; h.w1slab = w1slab; h.w1bslab = w1bslab;
-  h.N = N; h.H = H; h.W = W; h.tiles_x = (W + 63) / 64; h.tiles_y = (H + 3) / 4;
-  int dev = 0, ncu = 0;
-  CAN_HIP_CHECK(hipGetDevice(&dev));
-  CAN_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  const int ncu = can_device_cus();
   const int S = 2 * ws64_grid(N * h.tiles_y * h.tiles_x, ncu);
   if (S > slab_cap) return -12;
   const int rc = mbits != nullptr ? launch_ws64<DT, EPI_MASK, true, true>(h, s) : launch_ws64<DT, EPI_MASK, true>(h, s);
@@ -3000,38 +2765,54 @@ extern "C" int can_conv_pool_fwd(const void* x, const void* w, const float* bias
                                               (hipStream_t)stream, wv));
 }
 
-// the kernel configuration conv_igemm picks for a (non-first-layer) conv with tile_cfg 0: 31 = halo kernel (Cin = 64),
-// 33 = its weight-stationary ws64 form (Cin = Cout = 64), 27 / 28 / 29 = row ring, else the LDS-DMA tile config
+// Views of the launch plan under the process's dispatch config (conv_launch_plan in the bindings returns all of it).
+// The kernel configuration conv_igemm (EPI_POOLFWD: conv_pool_fwd) runs for a non-first-layer conv with tile_cfg 0:
+// 31 = halo kernel (Cin = 64), 33 = its weight-stationary ws64 form (Cin = Cout = 64), 27 / 28 / 29 = row ring, else
+// the LDS-DMA tile config; negative: the launcher's error for this shape
 extern "C" int can_conv_plan(int H, int W, int Cin, int Cout, int ksize, int dil, int epi) {
   using namespace can;
-  if (Cin == 64 && ksize == 3 && dil == 1 && (Cout == 64 || Cout == 128) && epi != EPI_SIGMOID &&
-      epi != EPI_POOLBWD && epi != EPI_F32)
-    return (Cout == 64 && use_ws64()) ? 33 : 31;
-  const int rr = (rring_mode() >= dil) ? rring_cfg(H, W, Cin, Cout, ksize, dil, epi) : 0;
-  return rr ? rr : glds_default_cfg(Cin, Cout, ksize);
+  const ConvPlan p = plan_conv({epi == EPI_POOLFWD ? ENTRY_POOL : ENTRY_IGEMM, 1, H, W, Cin, Cout, ksize, dil, epi},
+                               g_dispatch, 0);
+  return p.err ? p.err : p.cfg;
 }
 
-// split-K factor of the launch conv_igemm makes for this conv (tile_cfg 0): the row ring (cfg 27 / 29) or an LDS-DMA
-// v2 tile (cfg 21 / 22 / 23 / 25); 1 = no split (cfg 28, halo / weight-stationary kernels, large grids)
+// split-K factor of that launch; 1 = no split (cfg 28, halo / weight-stationary kernels, large grids, no launch)
 extern "C" int can_splitk_plan(int N, int H, int W, int Cin, int Cout, int ksize, int dil, int epi) {
   using namespace can;
-  const int cfg = can_conv_plan(H, W, Cin, Cout, ksize, dil, epi);
-  int tiles = 0;
-  size_t part = 0;                                // partial bytes per (tile, part)
-  if (cfg == 27 || cfg == 29) {
-    const int TC = (cfg == 27) ? 256 : 128;
-    tiles = (Cout / TC) * rr_np(H, W, N * H * W, 2);
-    part = (size_t)TC * 1024;
-  } else if (cfg == 21 || cfg == 22 || cfg == 23 || cfg == 25) {
-    const int TC = (cfg == 21) ? 256 : (cfg == 23) ? 64 : 128;
-    const int TP = (cfg == 21) ? 256 : (cfg == 22) ? 256 : 512;
-    tiles = (Cout / TC) * ((N * H * W + TP - 1) / TP);
-    part = (size_t)512 * 4 * 4 * ((cfg == 21 || cfg == 25) ? 2 : 1) * 16;   // 512 threads x 4 x 4 PW f32x4
-  } else {
-    return 1;
+  const ConvPlan p = plan_conv({epi == EPI_POOLFWD ? ENTRY_POOL : ENTRY_IGEMM, N, H, W, Cin, Cout, ksize, dil, epi},
+                               g_dispatch, can_device_cus());
+  return p.err ? 1 : p.ks;
+}
+
+// pixels of the pooling tile of the kernel conv_pool_fwd runs for this layer (tile_cfg 0 = default): the fused pool
+// needs H even and W % (tp / 2) == 0 (conv1_2's halo kernel: H % 4); 0: no such kernel.  Planned for a map that meets
+// every alignment
+extern "C" int can_conv_pool_tp(int Cin, int Cout, int ksize, int tile_cfg) {
+  using namespace can;
+  const ConvPlan p = plan_conv({ENTRY_POOL, 1, 4, 512, Cin, Cout, ksize, 1, EPI_POOLFWD, tile_cfg}, g_dispatch, 0);
+  return p.err ? 0 : pool_tile_px(*find_tile_cfg(p.cfg), Cout);
+}
+
+extern "C" int can_device_cus() {
+  static int ncu = 0;
+  if (ncu <= 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      ncu = 0;
   }
-  const int ks = splitk_ks(tiles, Cin, 2);
-  return ((size_t)tiles * ks * part > SK_PART_BYTES) ? 1 : ks;
+  return ncu;
+}
+
+extern "C" const void* can_zero_page() {
+  static void* z = nullptr;
+  if (!z) {
+    void* p = nullptr;
+    if (hipMalloc(&p, 4096) != hipSuccess) return nullptr;
+    if (hipMemset(p, 0, 4096) != hipSuccess) { (void)hipFree(p); return nullptr; }
+    z = p;
+  }
+  return z;
 }
 
 // arrival counters left non-zero (test hook: every split-K launch must leave all of them at zero); synchronises
@@ -3059,13 +2840,4 @@ extern "C" int can_splitk_slots_used() {
   int n = 0;
   for (int i = 0; i < SK_SLOTS; ++i) n += g_sk[dev][i].used;
   return n;
-}
-
-// pixels per tile of the kernel conv_pool_fwd runs for this layer (tile_cfg 0 = default): the fused pool
-// needs H even and W % (tp / 2) == 0
-extern "C" int can_conv_pool_tp(int Cin, int Cout, int ksize, int tile_cfg) {
-  if (Cin == 64 && Cout == 64 && ksize == 3 && tile_cfg == 0) return 128;   // halo kernel: W % 64 (and H % 4)
-  // row ring (2 x 128 tiles, 3x3 only): explicit cfg 27 (Cout % 256) / 29 (Cout % 128)
-  if (tile_cfg == 27 || tile_cfg == 29) return (ksize == 3 && Cout % (tile_cfg == 27 ? 256 : 128) == 0) ? 256 : 0;
-  return can::glds_cfg_tp(tile_cfg ? tile_cfg : can::glds_default_cfg(Cin, Cout, ksize));
 }

@@ -27,6 +27,7 @@
 //   <2,2,1>: 128 co x 128 k tile, 64-pixel stages, each wave 64x64 x 2 k-steps
 //   <1,1,4>: 64 co x 64 k tile, 128-pixel stages, each wave a 32-pixel quarter
 //            of every stage; the 4 partial tiles are summed through LDS.
+#include "api.h"
 #include "common.h"
 #include "fastdiv.h"
 #include <stdlib.h>
@@ -1150,13 +1151,8 @@ extern "C" int can_wgrad_plan(int M, int Cin, int Cout, int ksize, int first, in
   else cfg = 4;
   // the tap-ring kernel (wgrad_tap.inc) for the layers the v2 GEMM takes (dispatch wgrad_tap >= 1) and the Cout = 128
   // ones of the full-resolution ring kernel (>= 2); it needs the map width (W = 0: unknown, not chosen)
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-  }
+  int ncu = can_device_cus();
+  if (ncu <= 0) ncu = 256;                         // no device (host-only planning): an MI355X's count
   // the smallest slice count that fills whole rounds of one-block-per-CU launches to >= 90 %
   auto whole_rounds = [&](int ntile) {
     for (int R = 1; R <= 8; ++R) {
@@ -1214,14 +1210,6 @@ extern "C" int can_wgrad_plan(int M, int Cin, int Cout, int ksize, int first, in
   return 0;
 }
 
-static const can::bf16_t* zero_page() {
-  static void* z = nullptr;
-  if (!z) {
-    if (hipMalloc(&z, 4096) != hipSuccess) return nullptr;
-    if (hipMemset(z, 0, 4096) != hipSuccess) return nullptr;
-  }
-  return (const can::bf16_t*)z;
-}
 
 // Stream events from one ring (shared with the bindings' stream_wait): can_event_record returns the slot it recorded
 // on `stream`, can_event_wait makes `stream` wait for a slot.  Re-recording a slot whose earlier record is still
@@ -1312,7 +1300,7 @@ static int conv_wgrad_impl(const void* dy, const void* x, float* ws, float* wsb,
   } else {
     if (Cin % 64 || Cout % 64 || ((H < 2 || W < 2) && cfg != 12)) return -3;
     WgradArgs2 a;
-    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.zero = zero_page(); a.ws = ws; a.wsb = wsb_used;
+    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.zero = (const bf16_t*)can_zero_page(); a.ws = ws; a.wsb = wsb_used;
     if (!a.zero) return -7;
     a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = ksize; a.dil = dil; a.M = N * H * W; a.K = K;
     a.S = S; a.mslice = mslice;
@@ -1449,7 +1437,7 @@ static int conv_wgrad_1x1_batched_impl(const void* dy, const void* x, float* ws,
   using namespace can;
   if (Cout % 256 || Cin % 256 || W % 64 || mslice % 64 || M % 64 || (long long)M * Cout * 2 >= 0x7fffffffLL) return -3;
   WgradArgs2 a;
-  a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.zero = zero_page(); a.ws = ws; a.wsb = nullptr;
+  a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.zero = (const bf16_t*)can_zero_page(); a.ws = ws; a.wsb = nullptr;
   if (!a.zero) return -7;
   a.H = M / W; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = 1; a.dil = 1; a.M = M; a.K = Cin;
   a.S = S; a.mslice = mslice;

@@ -24,6 +24,7 @@ from . import _ext
 from . import dispatch
 
 EPI_BIAS_RELU, EPI_MASK, EPI_NONE, EPI_BIAS, EPI_SIGMOID, EPI_POOLBWD = 0, 1, 2, 3, 4, 5
+_EPI_POOLFWD, _ENTRY_POOL = 6, 1     # conv_pool_fwd's epilogue and planner entry (csrc/conv_plan.h)
 BF16 = torch.bfloat16
 ACT_DTYPES = {torch.bfloat16: 0, torch.float16: 1}   # -> kernel element-type code (csrc/common.h DT_*)
 
@@ -175,7 +176,7 @@ def conv_igemm(x: torch.Tensor, wpack: torch.Tensor, bias: Optional[torch.Tensor
         _check_bits(mask_bits_out, oshape, "mask_bits_out")
     if epi == EPI_POOLBWD:
         _check_codes(mask, (n, h, w, co))
-        if first or tile not in (0, 21, 22, 23, 25, 27, 28, 29):
+        if first or (tile != 0 and not _tile_caps(tile) & C.CAP_POOLBWD):
             raise ValueError("EPI_POOLBWD runs on the LDS-DMA kernels only")
     if out is None:
         out = torch.empty(*oshape, dtype=dt, device=x.device)
@@ -257,24 +258,28 @@ BIAS_ROWS = 512     # bias partial rows the weight-gradient reduce kernels take 
 
 def bias_part_capacity(n: int, h: int, w: int) -> int:
     """Rows a data-gradient epilogue may write for an output of n x h x w pixels (pooled resolution for
-    EPI_POOLBWD): LDS-DMA kernels one row per (pixel tile, wave slot) = ceil(M / 64) at most, the halo
-    kernel one per (4 x 64 tile, wave slot), the row ring one per (per-image 2- or 4-row x 128-column tile, wave
-    slot) (ragged tiles included)."""
-    cb = -(-w // 128)
-    return max(-(-n * h * w // 64) + 64, n * (-(-h // 4)) * (-(-w // 64)) * 8,
-               n * (-(-h // 2)) * cb * 4, n * (-(-h // 4)) * cb * 8)
+    EPI_POOLBWD): one row per (pixel tile, wave slot along the pixels), the maximum over the tile configs that write
+    partials (csrc/conv_plan.h), ragged tiles included."""
+    return _ext.require().bias_part_capacity(n, h, w)
+
+
+def _tile_caps(tile: int) -> int:
+    """Capability bits (csrc/conv_plan.h CAP_*) of a tile config; 0 for a number that is not one."""
+    entry = _ext.require().conv_tile_table().get(tile)
+    return entry["caps"] if entry else 0
 
 
 def mask_bits_ok(h: int, w: int, cin: int, cout: int, dil: int = 1) -> bool:
     """Whether the EPI_MASK data gradient [.., cin] -> [.., cout] at h x w runs on a kernel that takes sign bits."""
-    return _ext.require().conv_plan(h, w, cin, cout, 3, dil, EPI_MASK) in (21, 22, 23, 25)
+    return _ext.require().conv_launch_plan(1, h, w, cin, cout, 3, dil, EPI_MASK, mbits_in=True)["err"] == 0
 
 
 def mask_bits_out_ok(cin: int, cout: int, ksize: int = 3, dil: int = 1, first: bool = False) -> bool:
-    """Whether the ReLU forward of this conv can write its output's sign bits (first layer; Cin 64 -> Cout 128)."""
-    if ksize != 3 or dil != 1:
-        return False
-    return (cin in (3, 4) and cout == 64) if first else (cin == 64 and cout == 128)
+    """Whether the ReLU forward of this conv can write its output's sign bits (first layer; Cin 64 -> Cout 128):
+    the launch plan of such a conv (the check does not depend on the map size)."""
+    cin = 4 if first and cin == 3 else cin
+    return _ext.require().conv_launch_plan(1, 4, 128, cin, cout, ksize, dil, EPI_BIAS_RELU, first=int(first),
+                                           mbits_out=True)["err"] == 0
 
 
 def conv_dgrad_with_bias(dy: torch.Tensor, wpack: torch.Tensor, *, ksize: int, dil: int = 1, epi: int = EPI_MASK,
@@ -470,14 +475,11 @@ def conv_wgrad_1x1_batched(dy: torch.Tensor, x: torch.Tensor, dws, *, ws: "Wgrad
 
 
 def conv_pool_fwd_ok(x: torch.Tensor, cout: int, ksize: int, tile: int = 0) -> bool:
-    """Whether conv_pool_fwd covers this layer: H even and W a multiple of half the kernel's pixel tile."""
+    """Whether conv_pool_fwd covers this layer: H even (conv1_2's halo kernel: whole 4-row tiles) and W a multiple of
+    half the kernel's pixel tile: the launch plan of the dilation-1 layer has no error."""
     n, h, w, ci = x.shape
-    if ci % 64 or cout % 64 or h % 2 or h < 2 or w < 2:
-        return False
-    if ci == 64 and cout == 64 and ksize == 3 and tile == 0 and h % 4:
-        return False                       # conv1_2's halo kernel pools whole 4-row tiles
-    tp = _ext.require().conv_pool_tp(ci, cout, ksize, tile)
-    return tp > 0 and w % (tp // 2) == 0
+    return _ext.require().conv_launch_plan(n, h, w, ci, cout, ksize, 1, _EPI_POOLFWD, tile_cfg=tile,
+                                           entry=_ENTRY_POOL)["err"] == 0
 
 
 def conv_pool_fwd(x: torch.Tensor, wpack: torch.Tensor, bias: torch.Tensor, *, ksize: int, dil: int = 1,

@@ -390,7 +390,7 @@ class CANNetExecutor(ContextSchedule):
         return self.ws
 
     def _w1g_ok(self, x) -> bool:
-        """conv1_1's weight gradient fused into conv1_2's data gradient (conv_dgrad_w1g; CANNET_W1G=0: separate
+        """conv1_1's weight gradient fused into conv1_2's data gradient (conv_dgrad_w1g; dispatch w1g = 0: separate
         weight-gradient launch on the side stream).  Measured 453.5 -> 456.7 img/s, peak HBM 8.75 -> 7.95 GB
         (profiles/r2/ab_w1g.txt)."""
         f0, f1 = self.front[0], self.front[1]
@@ -422,9 +422,7 @@ class CANNetExecutor(ContextSchedule):
             ok = (t.idx == 1 and dispatch.current().w1g and s.cout == 64 and t.cin == 64 and t.cout == 64 and
                   x.shape[-1] == 4 and C.mask_bits_out_ok(4, 64, first=True))
         else:
-            ok = (C.mask_bits_out_ok(s.cin, s.cout) and
-                  self.C.conv_plan(h, w, s.cin, s.cout, 3, 1, C.EPI_BIAS_RELU) == 31 and
-                  C.mask_bits_ok(h, w, t.cout, t.cin, 1))
+            ok = C.mask_bits_out_ok(s.cin, s.cout) and C.mask_bits_ok(h, w, t.cout, t.cin, 1)
         if not ok:
             return None
         return torch.empty(n, h, w, s.cout // 8, dtype=torch.uint8, device=x.device)

@@ -263,7 +263,7 @@ def _check_pool_fwd(n, h, w, ci, co, dil, tile, dtype, seed=50):
 def test_pool_fwd_v2(n, h, w, ci, co, dil, cfg, dtype, dispatch_cfg):
     C, ext, _ = _mods()
     dispatch_cfg(splitk=0, rring_pool=0)
-    assert ext.conv_plan(h, w, ci, co, 3, dil, 6) == cfg   # EPI_POOLFWD: the LDS-DMA default tile
+    assert ext.conv_plan(h, w, ci, co, 3, dil, 6) == cfg   # EPI_POOLFWD: the config conv_pool_fwd launches
     _check_pool_fwd(n, h, w, ci, co, dil, 0, dtype)
 
 
