@@ -54,7 +54,11 @@ int can_head_fwd(const void* y, const float* w, const float* b, float* et, int P
                  int wv);
 int can_head_train(const void* y, const float* w, const float* b, const float* gt, float* et, void* dy, float* part,
                    int nblk, float* dw, float* db, float* loss, int P, float gscale, float beta, const float* lscale,
-                   float* nonfinite, int dt, void* stream, int pitch, int wv);
+                   float* nonfinite, int dt, void* stream, int pitch, int wv, const float* wt);
+// wt (null: none): the per-pixel loss weight, P floats indexed and padded like gt (head_train_kernel<DT, true>)
+// masked counts and GAME 0..3 per sample, two launches, fixed order: out [n][6] doubles = (E, G, GAME_0..GAME_3)
+int can_count_metrics(const float* et, const float* gt, long long gt_stride, const float* m, long long m_stride, int n,
+                      int h, int w, double* part, double* out, void* stream);
 int can_sgd_momentum(float* p, float* buf, const float* g, size_t n, float lr, float momentum, float gscale,
                      int first, float* flags, const float* lr_dev, void* stream, const float* gmul);
 int can_grad_nonfinite(const float* g, size_t n, float* flags, void* stream);
@@ -147,6 +151,14 @@ int can_preprocess_crop_scaled(const void* imgs, long long img_bytes, const long
 int can_preprocess_crop_photo(const void* imgs, long long img_bytes, const long long* desc, const long long* desc_host,
                               int n, void* x4, int CH, int CW, int ds, int dt, void* stream, const float* photo,
                               const float* photo_host, int scaled);
+// ROI weight plane of a packed batch of any kind whose images are 4-channel (the mask is the alpha byte): out
+// [n][2][CH/ds][CW/ds] fp32, plane 0 a copy of gt [n][CH/ds][CW/ds], plane 1 the weights (exact area means of alpha / 255
+// over each cell's source rectangle; 0 in the padding cells of an unscaled crop).  The check reads host memory only and
+// launches nothing: -31 an image that is not 4-channel, -32 a sample size that is no multiple of ds, -33 a window that
+// is empty or leaves its image (-2: any other bad argument); can_roi_weights runs it first and returns its code.
+int can_roi_weights_check(const long long* desc_host, int n, long long img_bytes, int CH, int CW, int ds);
+int can_roi_weights(const void* imgs, long long img_bytes, const long long* desc, const long long* desc_host, int n,
+                    const float* gt, float* out, int CH, int CW, int ds, void* stream);
 // synthetic batch: full-res densities [n][H][W] + coarse noise [n][3][H/16][W/16] -> x4 NHWC4, gt [n][H/8][W/8]
 int can_synth_render(const float* dens, const float* noise, float* dmax, void* x4, float* gt, int n, int H, int W,
                      int dt, void* stream);

@@ -151,12 +151,18 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(const uint4* __restrict__
 // dy[p][c] = det * S * w[c] * (y > 0) (S = device loss scale, 1 if null); partial dw[c] = sum_p det*y[p][c], db = sum det.
 // Per-block partials -> part[block][66] (64 dw, db, loss); reduced by head_reduce.  Padding columns of a
 // width-padded map (head_valid) add nothing to the loss or the gradients (et = 0, dy = 0 there).
-template <int DT>
+// WT (can_head_train with a weight plane): one more pointer, wt, P floats indexed and padded like gt, the per-pixel
+// loss weight m: dm = m * d (one fp32 product), loss += dm * d, det = (2 * dm) * gscale; et stays unweighted.  With
+// m = 1.0 dm is d itself, so every output is the WT = false kernel's bit for bit.
+__device__ __forceinline__ const float* head_wt(const float* wt) { return wt; }
+template <int DT, bool WT = false, typename... Wt>
 __global__ void __launch_bounds__(256) head_train_kernel(const uint4* __restrict__ y, const float* __restrict__ w,
                                                          const float* __restrict__ b, const float* __restrict__ gt,
                                                          float* __restrict__ et, uint4* __restrict__ dy,
                                                          float* __restrict__ part, int P, float gscale,
-                                                         const float* __restrict__ lscale, int pitch, int wv) {
+                                                         const float* __restrict__ lscale, int pitch, int wv,
+                                                         Wt... wt) {
+  static_assert(sizeof...(Wt) == (WT ? 1 : 0), "the weight plane is the one extra argument of a WT kernel");
   __shared__ float red[256 / 8][66];
   const float dys = (lscale != nullptr) ? lscale[0] : 1.f;   // loss scale: applied to dy only
   const int lane8 = threadIdx.x & 7;
@@ -178,8 +184,15 @@ __global__ void __launch_bounds__(256) head_train_kernel(const uint4* __restrict
     const bool valid = head_valid(p, pitch, wv);
     const float e = valid ? s + bias : 0.f;
     const float d = valid ? e - gt[p] : 0.f;
-    const float g = 2.f * d * gscale;
-    if (lane8 == 0) { et[p] = e; lossl += d * d; dbl += g; }
+    float g;
+    if constexpr (WT) {
+      const float dm = head_wt(wt...)[p] * d;
+      g = 2.f * dm * gscale;
+      if (lane8 == 0) { et[p] = e; lossl += dm * d; dbl += g; }
+    } else {
+      g = 2.f * d * gscale;
+      if (lane8 == 0) { et[p] = e; lossl += d * d; dbl += g; }
+    }
     float o[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -908,6 +921,77 @@ __global__ void accum_tick_kernel(float* __restrict__ flags, float* __restrict__
   }
 }
 
+// ---------------------------------------------------------------- count metrics (masked counts, GAME 0..3)
+// Per sample of et / gt [h][w] fp32 and an optional weight plane m (null: 1): level-l cell (a, b) covers rows
+// [(a h) >> l, ((a+1) h) >> l) and the columns likewise with w; every level's cells are unions of level-3 cells.
+// Stage 1, grid (64 level-3 cells, sample): block (c, s) sums double(m) * double(et) and double(m) * double(gt) (exact
+// products) over its cell, pixel k of the cell by thread k % 256, then reduces like grad_norm_partial_kernel: over the
+// wave by shuffles, over the four waves through LDS in wave order.  No atomics, fixed order: bitwise repeatable.  An
+// empty cell (a map smaller than 8) writes 0.  part: [n][64][2] doubles (E_cell, G_cell).
+__global__ void __launch_bounds__(256) count_metrics_kernel(const float* __restrict__ et, const float* __restrict__ gt,
+                                                            long long gt_stride, const float* __restrict__ m,
+                                                            long long m_stride, int h, int w,
+                                                            double* __restrict__ part) {
+  __shared__ double red[2][4];
+  const int a = blockIdx.x >> 3, b = blockIdx.x & 7;
+  const int r0 = (a * h) >> 3, r1 = ((a + 1) * h) >> 3, c0 = (b * w) >> 3, c1 = ((b + 1) * w) >> 3;
+  const int cw = c1 - c0, cnt = (r1 - r0) * cw;
+  const size_t s = blockIdx.y;
+  const float* e = et + s * (size_t)h * w;
+  const float* g = gt + s * (size_t)gt_stride;
+  const float* mm = (m != nullptr) ? m + s * (size_t)m_stride : nullptr;
+  double se = 0.0, sg = 0.0;
+  for (int k = threadIdx.x; k < cnt; k += 256) {
+    const size_t i = (size_t)(r0 + k / cw) * w + (c0 + k % cw);
+    const double wm = (mm != nullptr) ? (double)mm[i] : 1.0;
+    se = fma(wm, (double)e[i], se);
+    sg = fma(wm, (double)g[i], sg);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    se += __shfl_down(se, o, 64);
+    sg += __shfl_down(sg, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = se; red[1][threadIdx.x >> 6] = sg; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const double* r = red[threadIdx.x];
+    part[(s * 64 + blockIdx.x) * 2 + threadIdx.x] = ((r[0] + r[1]) + r[2]) + r[3];
+  }
+}
+
+// Stage 2, one block per sample: thread q < 85 owns cell q of the 1 + 4 + 16 + 64 cells of levels 0..3 and sums the
+// level-3 cells it is the union of in index order (rows, then columns), E and G apart; thread l < 4 then sums level l's
+// |E_cell - G_cell| in cell order.  out: [n][6] doubles = (E, G, GAME_0 .. GAME_3), E and G the level-0 sums.
+__global__ void __launch_bounds__(128) count_metrics_final_kernel(const double* __restrict__ part,
+                                                                  double* __restrict__ out) {
+  __shared__ double diff[85];
+  const double* p = part + (size_t)blockIdx.x * 128;
+  double* o = out + (size_t)blockIdx.x * 6;
+  const int q = threadIdx.x;
+  if (q < 85) {
+    const int l = (q >= 21) ? 3 : (q >= 5) ? 2 : (q >= 1) ? 1 : 0;
+    const int c = q - ((l == 3) ? 21 : (l == 2) ? 5 : (l == 1) ? 1 : 0);
+    const int side = 1 << l, span = 8 >> l;
+    const int a = c / side, b = c % side;
+    double se = 0.0, sg = 0.0;
+    for (int i = a * span; i < (a + 1) * span; ++i)
+      for (int j = b * span; j < (b + 1) * span; ++j) {
+        se += p[(i * 8 + j) * 2];
+        sg += p[(i * 8 + j) * 2 + 1];
+      }
+    diff[q] = fabs(se - sg);
+    if (q == 0) { o[0] = se; o[1] = sg; }
+  }
+  __syncthreads();
+  if (q < 4) {
+    const int first = (q == 3) ? 21 : (q == 2) ? 5 : (q == 1) ? 1 : 0, cells = 1 << (2 * q);
+    double sd = 0.0;
+    for (int c = 0; c < cells; ++c) sd += diff[first + c];
+    o[2 + q] = sd;
+  }
+}
+
 static inline int grid_for(size_t n, int per = 256, int cap = 4096) {
   size_t g = (n + per - 1) / per;
   if (g > (size_t)cap) g = cap;
@@ -958,9 +1042,15 @@ extern "C" int can_head_fwd(const void* y, const float* w, const float* b, float
 extern "C" int can_head_train(const void* y, const float* w, const float* b, const float* gt, float* et, void* dy,
                               float* part, int nblk, float* dw, float* db, float* loss, int P, float gscale,
                               float beta, const float* lscale, float* nonfinite, int dt, void* stream, int pitch,
-                              int wv) {
+                              int wv, const float* wt) {
   hipStream_t s = (hipStream_t)stream;
-  if (dt == DT_F16)
+  if (wt != nullptr && dt == DT_F16)
+    hipLaunchKernelGGL((head_train_kernel<DT_F16, true>), dim3(nblk), dim3(256), 0, s, (const uint4*)y, w, b, gt, et,
+                       (uint4*)dy, part, P, gscale, lscale, pitch, wv, wt);
+  else if (wt != nullptr && dt == DT_BF16)
+    hipLaunchKernelGGL((head_train_kernel<DT_BF16, true>), dim3(nblk), dim3(256), 0, s, (const uint4*)y, w, b, gt, et,
+                       (uint4*)dy, part, P, gscale, lscale, pitch, wv, wt);
+  else if (dt == DT_F16)
     hipLaunchKernelGGL(head_train_kernel<DT_F16>, dim3(nblk), dim3(256), 0, s, (const uint4*)y, w, b, gt, et,
                        (uint4*)dy, part, P, gscale, lscale, pitch, wv);
   else if (dt == DT_BF16)
@@ -1199,6 +1289,20 @@ extern "C" int can_grad_norm(const float* g, const long long* tab, int np, long 
   hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(max_chunks, np), dim3(256), 0, s, g, tab, part, max_chunks);
   hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, s, tab, np, part, max_chunks, gn, gscale, max_norm,
                      flag);
+  return (int)hipGetLastError();
+}
+
+// Count metrics of n samples (count_metrics_kernel + count_metrics_final_kernel): et [n][h][w] contiguous, gt and the
+// optional weight plane m (null: 1) [h][w] planes gt_stride / m_stride floats apart from sample to sample (so the two
+// channels of a [n,2,h,w] tensor are read in place), part: n * 128 doubles of scratch, out: [n][6] doubles.
+extern "C" int can_count_metrics(const float* et, const float* gt, long long gt_stride, const float* m,
+                                 long long m_stride, int n, int h, int w, double* part, double* out, void* stream) {
+  if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || (long long)h * w > 0x0fffffff) return -2;
+  if (et == nullptr || gt == nullptr || part == nullptr || out == nullptr) return -2;
+  if (gt_stride < (long long)h * w || (m != nullptr && m_stride < (long long)h * w)) return -2;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(count_metrics_kernel, dim3(64, n), dim3(256), 0, s, et, gt, gt_stride, m, m_stride, h, w, part);
+  hipLaunchKernelGGL(count_metrics_final_kernel, dim3(n), dim3(128), 0, s, (const double*)part, out);
   return (int)hipGetLastError();
 }
 

@@ -240,6 +240,58 @@ __global__ void __launch_bounds__(256) preprocess_resample_kernel(const unsigned
   }
 }
 
+// ROI weight plane of a pack whose images are 4-channel, the mask in the alpha byte (README, "ROI masks").  Grid
+// (16 x 16 cell tile, sample), one cell per thread.  The window is read from the descriptor as the image kernels and
+// gt_from_heads_kernel read it: the whole image for slot 7 == 0, the valid (vh, vw) of the crop at (y0, x0) for 1 (its
+// cells exact ds x ds boxes, the padding cells 0), [y0, y0+sh) x [x0, x0+sw) otherwise.  Cell (i, j) of a window cut
+// into R x Q cells covers rows [i sh / R, (i+1) sh / R) and the columns of j' = Q-1-j when flipped; with the integer
+// overlap numerators oy_i(t) = min((t+1) R, (i+1) sh) - max(t R, i sh) and ox likewise,
+//   S = sum_t sum_u oy_i(t) ox_j'(u) alpha[y0+t][x0+u]   (int64),   m = float(double(S) / double(255 sh sw)):
+// integers up to one division, so the host rule (data/transforms.py:roi_weights) gives the same bits.  It reads no
+// byte outside the window.  out [n][2][rows][cols]: plane 0 = gt (the pack's ground truth region), plane 1 = m.
+__global__ void __launch_bounds__(256) roi_weights_kernel(const unsigned char* __restrict__ imgs,
+                                                          const long long* __restrict__ desc,
+                                                          const float* __restrict__ gt, float* __restrict__ out,
+                                                          int rows, int cols, int ds) {
+  const Desc s = load_desc(desc);
+  const int tiles_x = (cols + 15) / 16;
+  const int i = (blockIdx.x / tiles_x) * 16 + (threadIdx.x >> 4), j = (blockIdx.x % tiles_x) * 16 + (threadIdx.x & 15);
+  if (i >= rows || j >= cols) return;
+  long long y0 = s.y0, x0 = s.x0, sh, sw;
+  int R = rows, Q = cols;
+  if (s.ext == 0) {
+    y0 = 0; x0 = 0; sh = s.H0; sw = s.W0;
+  } else if (s.ext == 1) {
+    R = min(rows, s.H0 / ds); Q = min(cols, s.W0 / ds);
+    sh = (long long)R * ds; sw = (long long)Q * ds;
+  } else {
+    sh = s.ext >> 32; sw = s.ext & 0xffffffffll;
+  }
+  const size_t plane = (size_t)rows * cols;
+  const size_t o = (size_t)blockIdx.y * 2 * plane + (size_t)i * cols + j;
+  out[o] = gt[(size_t)blockIdx.y * plane + (size_t)i * cols + j];
+  float m = 0.f;
+  if (i < R && j < Q) {
+    const long long jj = s.flip ? Q - 1 - j : j;
+    const long long ta = (i * sh) / R, tb = ((i + 1) * sh + R - 1) / R;
+    const long long ua = (jj * sw) / Q, ub = ((jj + 1) * sw + Q - 1) / Q;
+    const unsigned char* alpha = imgs + s.off + 3;
+    long long S = 0;
+    for (long long t = ta; t < tb; ++t) {
+      const long long oy = min((t + 1) * R, (i + 1) * sh) - max(t * R, i * sh);
+      const unsigned char* row = alpha + ((size_t)(y0 + t) * s.W0 + x0) * 4;
+      long long rs = 0;
+      for (long long u = ua; u < ub; ++u) {
+        const long long ox = min((u + 1) * Q, (jj + 1) * sw) - max(u * Q, jj * sw);
+        rs += ox * row[(size_t)u * 4];
+      }
+      S += oy * rs;
+    }
+    m = (float)((double)S / (double)(255ll * sh * sw));
+  }
+  out[o + plane] = m;
+}
+
 // ---------------------------------------------------------------------------
 // Synthetic crowd batch on the GPU (train.py --synthetic / bench data; data/synthetic.py is the CPU
 // reference of the same recipe): per image, head points (host RNG, tiny) -> fixed-sigma Gaussian
@@ -442,6 +494,48 @@ extern "C" int can_preprocess_crop_photo(const void* imgs, long long img_bytes, 
                           photo);
   else
     return -20;
+  return (int)hipGetLastError();
+}
+
+// The host descriptors of a roi launch, each refusal with its own code (api.h): every image 4-channel (-31), the sample
+// a multiple of ds (-32), every window non-empty and inside its image, the image inside img_bytes (-33).
+extern "C" int can_roi_weights_check(const long long* desc_host, int n, long long img_bytes, int CH, int CW, int ds) {
+  if (desc_host == nullptr || n <= 0 || n > 65535 || ds <= 0 || CH <= 0 || CW <= 0 || img_bytes < 0) return -2;
+  if ((long long)CH * CW > 0x7fffffff) return -2;
+  for (int i = 0; i < n; ++i)
+    if (desc_host[(size_t)i * 8 + 3] != 4) return -31;
+  if (CH % ds || CW % ds) return -32;
+  for (int i = 0; i < n; ++i) {
+    const long long* d = desc_host + (size_t)i * 8;
+    const long long H0 = d[1], W0 = d[2];
+    long long eh, ew;
+    if (d[7] == 0) {                       // whole image: the sample is its largest multiple of ds
+      if (d[5] != 0 || d[6] != 0 || H0 / ds * ds != CH || W0 / ds * ds != CW) return -33;
+      eh = H0;
+      ew = W0;
+    } else if (d[7] == 1) {
+      eh = H0 / ds * ds < CH ? H0 / ds * ds : CH;
+      ew = W0 / ds * ds < CW ? W0 / ds * ds : CW;
+    } else {
+      eh = d[7] >> 32;
+      ew = d[7] & 0xffffffffll;
+      if (d[7] < 0 || eh < 1 || ew < 1) return -33;
+    }
+    if (!crop_desc_ok(d, img_bytes, eh, ew)) return -33;
+  }
+  return 0;
+}
+
+extern "C" int can_roi_weights(const void* imgs, long long img_bytes, const long long* desc,
+                               const long long* desc_host, int n, const float* gt, float* out, int CH, int CW, int ds,
+                               void* stream) {
+  using namespace can;
+  if (imgs == nullptr || desc == nullptr || gt == nullptr || out == nullptr) return -2;
+  const int rc = can_roi_weights_check(desc_host, n, img_bytes, CH, CW, ds);
+  if (rc) return rc;
+  const int rows = CH / ds, cols = CW / ds;
+  hipLaunchKernelGGL(roi_weights_kernel, dim3(((rows + 15) / 16) * ((cols + 15) / 16), n), dim3(256), 0,
+                     (hipStream_t)stream, (const unsigned char*)imgs, desc, gt, out, rows, cols, ds);
   return (int)hipGetLastError();
 }
 

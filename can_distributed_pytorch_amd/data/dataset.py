@@ -39,7 +39,7 @@ import torch
 from torch.utils.data import Dataset
 
 from .transforms import (_axis_weights, apply_photo, area_factor, heads_to_gt, heads_to_gt_padded, photo_table,
-                         prepare_pair, prepare_pair_scaled)
+                         prepare_pair, prepare_pair_scaled, roi_weights, roi_weights_padded)
 
 IMG_EXT = (".jpg", ".jpeg", ".png", ".bmp", ".tif", ".tiff")
 _M64 = (1 << 64) - 1
@@ -226,8 +226,14 @@ def imread(path: str) -> np.ndarray:
 class CrowdDataset(Dataset):
     def __init__(self, img_root: str, gt_dmap_root: str, gt_downsample: int = 1, phase: str = "train",
                  seed: Optional[int] = None, raw: bool = False, crop=None, crops_per_image: int = 1,
-                 crop_scale=None, gt_from_heads: bool = False, photo_jitter=None, gray_prob: float = 0.0):
+                 crop_scale=None, gt_from_heads: bool = False, photo_jitter=None, gray_prob: float = 0.0,
+                 roi: bool = False):
         self.img_root = img_root
+        # roi=True: every image has an ROI mask ground_truth/NAME.roi.npy (data/density.py:roi_path).  raw=False items
+        # carry a 2-channel ground truth (the ground truth, the per-cell loss weight of transforms.roi_weights);
+        # raw=True items carry the image as uint8 [H0, W0, 4] with the mask as its alpha channel and the GPU renders
+        # the weights (ops/preprocess.py roi=True).  Every phase and kind alike.
+        self.roi = bool(roi)
         self.gt_dmap_root = gt_dmap_root
         self.gt_downsample = max(1, int(gt_downsample))
         self.phase = phase
@@ -294,6 +300,28 @@ class CrowdDataset(Dataset):
             raise ValueError(f"{path}: head records must be [N, 4] of (c, r, sigma, R), got {tuple(heads.shape)}")
         return np.ascontiguousarray(heads, dtype=np.float32)
 
+    def load_roi(self, name: str, h0: int, w0: int) -> np.ndarray:
+        """The ROI mask uint8 [h0, w0] of image ``name``; a missing or mis-shaped one is a ValueError naming the file."""
+        from .density import roi_path
+        path = roi_path(self.gt_path(name))
+        if not os.path.isfile(path):
+            raise ValueError(f"{name}: no ROI mask {path} (uint8 [H0, W0], 255 inside the region of interest)")
+        mask = np.load(path)                                     # allow_pickle=False (default)
+        if mask.dtype != np.uint8 or tuple(mask.shape) != (h0, w0):
+            raise ValueError(f"{path}: an ROI mask is uint8 {(h0, w0)} like its image, got {mask.dtype} "
+                             f"{tuple(mask.shape)}")
+        return np.ascontiguousarray(mask)
+
+    @staticmethod
+    def _with_alpha(img: np.ndarray, mask: np.ndarray) -> np.ndarray:
+        """uint8 [H0, W0, 4]: the image's three colour channels (a gray image's value three times) and the mask as
+        alpha; an alpha channel of the image's own is replaced."""
+        img = _as_uint8(img)
+        rgb = np.repeat(img[:, :, None], 3, axis=2) if img.ndim == 2 else img[:, :, :3]
+        if rgb.shape[2] != 3:
+            raise ValueError(f"an image is L, RGB or RGBA, got {tuple(img.shape)}")
+        return np.ascontiguousarray(np.concatenate([rgb, mask[:, :, None]], axis=2))
+
     def __getitem__(self, index):
         epoch = self.epoch
         if isinstance(index, (tuple, list)):
@@ -305,15 +333,21 @@ class CrowdDataset(Dataset):
         if self.crop is not None:
             return self._crop_item(img, name, epoch, index)
         flip = self.phase == "train" and flip_draw(self.seed, epoch, index)
+        d = self.gt_downsample
+        mask = self.load_roi(name, img.shape[0], img.shape[1]) if self.roi else None
         if self.raw:
             # the GPU resizes / normalises the image; the ground truth is brought to its 1/d resolution here,
             # reading only the source rows the bilinear taps touch (memory-mapped: ~1/4 of a full-resolution
             # fp32 map), so a batch moves ~8x fewer host bytes than shipping full-resolution densities
             dmap = np.load(self.gt_path(name), mmap_mode="r")        # allow_pickle=False (default)
             gt = density_to_gt(dmap, img.shape[0], img.shape[1], self.gt_downsample, flip)
-            return torch.from_numpy(_as_uint8(img)), torch.from_numpy(gt), flip
+            img = _as_uint8(img) if mask is None else self._with_alpha(img, mask)
+            return torch.from_numpy(img), torch.from_numpy(gt), flip
         dmap = np.load(self.gt_path(name))                       # allow_pickle=False (default)
         im, dm = prepare_pair(img, dmap, self.gt_downsample, flip)
+        if mask is not None:
+            h0, w0 = mask.shape
+            dm = np.concatenate([dm, roi_weights(mask, 0, 0, h0, w0, h0 // d, w0 // d, flip)[None]])
         return torch.from_numpy(np.ascontiguousarray(im)), torch.from_numpy(np.ascontiguousarray(dm))
 
 
@@ -332,13 +366,14 @@ class CrowdDataset(Dataset):
         h0, w0 = img.shape[:2]
         scaled = self.crop_scale is not None
         if self.gt_from_heads:
-            return self._crop_item_heads(img, self.load_heads(name), epoch, index, scaled)
+            return self._crop_item_heads(img, self.load_heads(name), epoch, index, scaled, name)
         dmap = np.load(self.gt_path(name), mmap_mode="r" if self.raw else None)      # allow_pickle=False (default)
         if tuple(dmap.shape) != (h0, w0):
             raise ValueError(f"{name}: density map {tuple(dmap.shape)} differs from its image {(h0, w0)}: a crop "
                              "takes the same window of both")
         ims, gts, rows = [], [], []
         photo = self._photo_rows(epoch, index)
+        mask = self.load_roi(name, h0, w0) if self.roi else None
         for k in range(K):
             if scaled:
                 wh, ww = scaled_window(h0, w0, ch, cw, scale_draw(self.seed, epoch, index, k, *self.crop_scale))
@@ -355,11 +390,22 @@ class CrowdDataset(Dataset):
                 im, gt = prepare_pair_scaled(im, dm, ch, cw, d, fl) if scaled else prepare_pair(im, dm, d, fl)
                 ims.append(_pad_to(im, ch, cw))
             gts.append(_pad_to(gt, ch // d, cw // d))
+            if mask is not None and not self.raw:
+                gts[-1] = np.concatenate([gts[-1], self._crop_weights(mask, y0, x0, wh, ww, fl, scaled)[None]])
         gts = torch.from_numpy(np.stack(gts))
         if self.raw:
-            return (torch.from_numpy(_as_uint8(img)), gts, torch.tensor(rows, dtype=torch.int64)) + \
+            img = _as_uint8(img) if mask is None else self._with_alpha(img, mask)
+            return (torch.from_numpy(img), gts, torch.tensor(rows, dtype=torch.int64)) + \
                 (() if photo is None else (torch.from_numpy(photo),))
         return torch.from_numpy(np.stack(ims)), gts
+
+    def _crop_weights(self, mask: np.ndarray, y0: int, x0: int, wh: int, ww: int, fl: bool, scaled: bool):
+        """The loss weights fp32 [ch/d, cw/d] of one crop window: roi_weights of a scaled window, roi_weights_padded
+        (0 in the padding cells) of an unscaled one."""
+        d, (ch, cw) = self.gt_downsample, self.crop
+        if scaled:
+            return roi_weights(mask, y0, x0, wh, ww, ch // d, cw // d, fl)
+        return roi_weights_padded(mask, y0, x0, ch, cw, d, fl)
 
     def _photo_rows(self, epoch: int, index: int):
         """float32 [K, 257], crop k's tone table (photo_table of its photo_draw) and gray flag 0.0 / 1.0; None with the
@@ -373,12 +419,13 @@ class CrowdDataset(Dataset):
             out[k, 256] = float(gray)
         return out
 
-    def _crop_item_heads(self, img: np.ndarray, heads: np.ndarray, epoch: int, index: int, scaled: bool):
+    def _crop_item_heads(self, img: np.ndarray, heads: np.ndarray, epoch: int, index: int, scaled: bool, name=None):
         """_crop_item with the ground truth from head records: the windows and flips are the same draws."""
         d, (ch, cw), K = self.gt_downsample, self.crop, self.crops_per_image
         h0, w0 = img.shape[:2]
         ims, gts, rows = [], [], []
         photo = self._photo_rows(epoch, index)
+        mask = self.load_roi(name, h0, w0) if self.roi else None
         for k in range(K):
             if scaled:
                 wh, ww = scaled_window(h0, w0, ch, cw, scale_draw(self.seed, epoch, index, k, *self.crop_scale))
@@ -395,8 +442,11 @@ class CrowdDataset(Dataset):
             ims.append(_pad_to(im, ch, cw))
             gts.append(heads_to_gt(heads, h0, w0, (y0, x0, wh, ww), ch, cw, d, fl) if scaled else
                        heads_to_gt_padded(heads, h0, w0, y0, x0, ch, cw, d, fl))
+            if mask is not None:
+                gts[-1] = np.concatenate([gts[-1], self._crop_weights(mask, y0, x0, wh, ww, fl, scaled)[None]])
         if self.raw:
-            return (torch.from_numpy(_as_uint8(img)), torch.from_numpy(heads), torch.tensor(rows, dtype=torch.int64)) + \
+            img = _as_uint8(img) if mask is None else self._with_alpha(img, mask)
+            return (torch.from_numpy(img), torch.from_numpy(heads), torch.tensor(rows, dtype=torch.int64)) + \
                 (() if photo is None else (torch.from_numpy(photo),))
         return torch.from_numpy(np.stack(ims)), torch.from_numpy(np.stack(gts))
 

@@ -99,6 +99,12 @@ def heads_path(npy_path: str) -> str:
     return os.path.splitext(npy_path)[0] + ".heads.npy"
 
 
+def roi_path(npy_path: str) -> str:
+    """ground_truth/IMG_k.npy -> ground_truth/IMG_k.roi.npy, the image's ROI mask: uint8 [H0, W0], 255 inside, 0
+    outside, a in between the fraction a / 255."""
+    return os.path.splitext(npy_path)[0] + ".roi.npy"
+
+
 def density_map_gpu(points, h: int, w: int, device="cuda", max_radius: int = 0) -> torch.Tensor:
     """GPU density map [h, w] fp32 for points [[x, y], ...].  Not bitwise reproducible (fp32 atomics); measured on
     one MI355X against an fp64 reference (tests/test_gpu_density.py): the kNN sigma within 0.34 * 8 * 2^-24 relative,

@@ -207,3 +207,49 @@ def heads_to_gt_padded(heads: np.ndarray, h0: int, w0: int, y0: int, x0: int, ch
     if vh and vw:
         out[:, :vh // d, :vw // d] = heads_to_gt(heads, h0, w0, (y0, x0, vh, vw), vh, vw, d, flip)
     return out
+
+
+def _overlap_numerators(ext: int, cells: int) -> np.ndarray:
+    """int64 [cells, ext]: oy_i(t) = max(0, min((t+1) cells, (i+1) ext) - max(t cells, i ext)), the length of source
+    pixel t inside cell i of an axis of extent ``ext`` cut into ``cells`` cells, times ``cells``.  Every row sums to
+    ``ext``."""
+    t = np.arange(ext, dtype=np.int64)[None, :]
+    i = np.arange(cells, dtype=np.int64)[:, None]
+    return np.maximum(0, np.minimum((t + 1) * cells, (i + 1) * ext) - np.maximum(t * cells, i * ext))
+
+
+def roi_weights(mask_u8: np.ndarray, y0: int, x0: int, sh: int, sw: int, rows: int, cols: int,
+                flip: bool = False) -> np.ndarray:
+    """The per-cell loss weight of a window of an ROI mask (uint8 [H0, W0], 255 inside, 0 outside, a in between the
+    fraction a / 255): cell (i, j) of the (rows, cols) grid is the exact area mean of mask / 255 over the source
+    rectangle it covers in the window (y0, x0, sh, sw), the rectangle of heads_to_gt, mirrored columns when flipped:
+    S = sum_t sum_u oy_i(t) ox_j'(u) a[y0+t][x0+u] in int64, m = float32(float64(S) / float64(255 sh sw)).  All-integer
+    up to the one division, so csrc/preprocess.hip roi_weights_kernel gives the same bits; an all-255 window gives
+    exactly 1.0.  Returns fp32 [rows, cols]."""
+    y0, x0, sh, sw, rows, cols = (int(v) for v in (y0, x0, sh, sw, rows, cols))
+    mask_u8 = np.asarray(mask_u8)
+    if mask_u8.ndim != 2 or mask_u8.dtype != np.uint8:
+        raise ValueError(f"an ROI mask is uint8 [H0, W0], got {mask_u8.dtype} {tuple(mask_u8.shape)}")
+    h0, w0 = mask_u8.shape
+    if rows < 1 or cols < 1:
+        raise ValueError(f"a weight plane needs rows, cols >= 1, got {(rows, cols)}")
+    if sh < 1 or sw < 1 or y0 < 0 or x0 < 0 or y0 + sh > h0 or x0 + sw > w0:
+        raise ValueError(f"window {(y0, x0, sh, sw)} is empty or leaves its {h0}x{w0} mask")
+    a = mask_u8[y0:y0 + sh, x0:x0 + sw].astype(np.int64)
+    s = _overlap_numerators(sh, rows) @ a @ _overlap_numerators(sw, cols).T
+    m = (s.astype(np.float64) / np.float64(255 * sh * sw)).astype(np.float32)
+    return np.ascontiguousarray(m[:, ::-1]) if flip else m
+
+
+def roi_weights_padded(mask_u8: np.ndarray, y0: int, x0: int, ch: int, cw: int, downsample: int = 8,
+                       flip: bool = False) -> np.ndarray:
+    """roi_weights for the UNSCALED crop at (y0, x0) of an image that may be smaller than the crop: the valid (vh, vw)
+    = crop_window extent is rendered (every cell an exact d x d box, flipped within the valid columns) and the cells of
+    the zero padding are 0, so the padding takes no part in the loss.  Returns fp32 [ch/d, cw/d]."""
+    d = int(downsample)
+    h0, w0 = np.asarray(mask_u8).shape
+    vh, vw = min(ch, h0 // d * d), min(cw, w0 // d * d)
+    out = np.zeros((ch // d, cw // d), dtype=np.float32)
+    if vh and vw:
+        out[:vh // d, :vw // d] = roi_weights(mask_u8, y0, x0, vh, vw, vh // d, vw // d, flip)
+    return out

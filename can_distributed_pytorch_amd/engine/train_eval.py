@@ -27,6 +27,7 @@ from typing import Optional
 import torch
 
 from ..parallel.distributed import is_main_process, reduce_value, get_world_size
+from .metrics import weighted_sq_loss
 
 
 def _progress(it, enabled):
@@ -50,7 +51,7 @@ def train_one_epoch(model, optimizer, train_loader, device, epoch, log=None, acc
     torch.nn.utils.clip_grad_norm_ ahead of every optimizer step.  on_step: called after every optimizer step (the
     EMA update of the stepper that owns the optimizer)."""
     model.train()
-    criterion = torch.nn.MSELoss(reduction="sum")
+    criterion = weighted_sq_loss                  # MSELoss(sum); a 2-channel gt carries a loss weight
     mean_loss = torch.zeros(1, device=device)
     loader = _progress(train_loader, is_main_process())
     params = [p for p in model.parameters() if p.requires_grad]

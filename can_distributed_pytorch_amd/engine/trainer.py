@@ -22,6 +22,7 @@ import torch
 import torch.distributed as dist
 
 from ..models.cannet import CANNet
+from .metrics import weighted_sq_loss
 
 
 OPTIMIZERS = ("sgd", "adam", "adamw")
@@ -172,7 +173,7 @@ class TorchStepper(ParamEma):
         self.opt = make_torch_optimizer([p for p in self.model.parameters() if p.requires_grad], optimizer,
                                         lr=lr * world, momentum=momentum, weight_decay=weight_decay, betas=betas,
                                         eps=eps)
-        self.crit = torch.nn.MSELoss(reduction="sum")
+        self.crit = weighted_sq_loss                  # MSELoss(sum); a 2-channel gt carries a loss weight
         self._loss = None
         self.autocast = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(dtype)
         self.scaler = torch.amp.GradScaler("cuda") if dtype == "fp16" else None
@@ -296,7 +297,7 @@ class ArenaStepper(ParamEma):
         self.reducer = BucketedReducer(self.arena, order, bucket_mb=bucket_mb, transport="torch")
         self.reducer.attach_hooks()
         self.flags = torch.zeros(2, dtype=torch.float32, device=self.device)
-        self.crit = torch.nn.MSELoss(reduction="sum")
+        self.crit = weighted_sq_loss                  # MSELoss(sum); a 2-channel gt carries a loss weight
         self.comm_timing = False
         self._timings = []
         self._loss = None

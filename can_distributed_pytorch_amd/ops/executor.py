@@ -681,18 +681,30 @@ class CANNetExecutor(ContextSchedule):
         flags: optional fp32 device vector; the loss is written to flags[1] and its non-finite flag
         (1.0 / 0.0) to flags[0] by the same reduction kernel (the returned loss is then flags[1:2]).
         wvalid: b6 is width-padded with this valid width (default: the last forward's); gt is at the valid width,
-        the padding columns add nothing to the loss or the gradients and et is returned at the valid width."""
+        the padding columns add nothing to the loss or the gradients and et is returned at the valid width.
+        gt [n,2,h,wg] fp32: channel 0 the ground truth, channel 1 a per-pixel loss weight m (loss = sum m (et-gt)^2,
+        head_train_kernel<DT, true>); et stays unweighted.  A [n,1,h,wg] gt issues exactly the unweighted launch."""
         n, h, w, c = b6.shape
         wvalid = self.last_wvalid if wvalid is None else wvalid
         wv = C._wv(wvalid, w)
         wg = wv or w
-        if tuple(gt.shape) != (n, 1, h, wg):
-            raise ValueError(f"gt shape {tuple(gt.shape)} != {(n, 1, h, wg)}")
+        wt = None
+        if tuple(gt.shape) == (n, 2, h, wg):
+            # ground truth and per-pixel loss weight in one tensor (README, "ROI masks"): two contiguous planes
+            if gt.dtype != torch.float32:
+                raise ValueError(f"a 2-channel gt (ground truth, loss weight) must be fp32, got {gt.dtype}")
+            gt, wt = gt[:, 0:1].contiguous(), gt[:, 1:2].contiguous()
+        elif tuple(gt.shape) != (n, 1, h, wg):
+            raise ValueError(f"gt shape {tuple(gt.shape)} != {(n, 1, h, wg)} (or {(n, 2, h, wg)} with a loss weight)")
         gt = gt.float().contiguous()
         if wv:
             gp = torch.zeros(n, 1, h, w, dtype=torch.float32, device=gt.device)
             gp[..., :wv].copy_(gt)
             gt = gp
+            if wt is not None:
+                wp = torch.zeros(n, 1, h, w, dtype=torch.float32, device=gt.device)
+                wp[..., :wv].copy_(wt)
+                wt = wp
         P = n * h * w
         et = torch.empty(n, 1, h, w, dtype=torch.float32, device=b6.device)
         d_b6 = torch.empty_like(b6)
@@ -708,7 +720,7 @@ class CANNetExecutor(ContextSchedule):
                           gt.data_ptr(), et.data_ptr(), d_b6.data_ptr(), part.data_ptr(), nblk,
                           grads[self.head_w_index].data_ptr(), grads[self.head_b_index].data_ptr(), loss.data_ptr(),
                           P, float(gscale), float(beta), lscale.data_ptr() if lscale is not None else 0, nf, self.dt,
-                          self._stream(), w if wv else 0, wv)
+                          self._stream(), w if wv else 0, wv, *(() if wt is None else (wt.data_ptr(),)))
         return loss, (et[..., :wv] if wv else et), d_b6
 
     # ----------------------------------------------------------- autograd entry

@@ -231,9 +231,12 @@ def _unpack(packed):
     return buf, (n, ho, wo, goff, doff), KINDS[len(meta) - 5]
 
 
-def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device):
+def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device, roi=False):
     """The one launch of a pack of any kind: d, the device copy of buf -> (x4, gt), gt a view of d.  The crop entries
-    check the host descriptors (in buf) before they launch, the photo entry the host photo rows as well."""
+    check the host descriptors (in buf) before they launch, the photo entry the host photo rows as well.
+    roi: the pack's images are 4-channel with the ROI mask as alpha (CrowdDataset(roi=True)); after the pack's other
+    launches, on the same stream, roi_weights_kernel writes gt2 [n,2,ho/d,wo/d] (the ground truth, the loss weights)
+    and (x4, gt2) is returned.  Its check runs on the host descriptors before ANY launch."""
     hd, wd = ho // downsample, wo // downsample
     gt = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
     desc = d[doff:doff + 64 * n].view(torch.int64).view(n, 8)
@@ -242,6 +245,11 @@ def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device):
     kind, *flags = kind.split("+")
     heads, photo = "heads" in flags, "photo" in flags
     poff = buf.numel() - (4 * PackedCollate.PHOTO_ROW * n if photo else 0)      # the photo region ends the buffer
+    if roi:
+        rc = C.roi_weights_check(buf.data_ptr() + doff, n, goff, ho, wo, downsample)
+        if rc:
+            raise RuntimeError(f"roi_weights refused the pack (code {rc}: -31 an image without a mask channel, -32 a "
+                               "sample size that is no multiple of the downsample, -33 a window outside its image)")
     if heads:
         # checked on the host copies before EITHER launch (a refused pack launches nothing); the render itself is
         # issued right after the image launch, on the same stream
@@ -262,15 +270,21 @@ def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device):
     if heads:
         C.gt_from_heads(d.data_ptr() + hoff, d.data_ptr() + roff, desc.data_ptr(), buf.data_ptr() + hoff, nh,
                         buf.data_ptr() + roff, buf.data_ptr() + doff, n, gt.data_ptr(), ho, wo, downsample, tail[-1])
+    if roi:
+        gt2 = torch.empty(n, 2, hd, wd, dtype=torch.float32, device=device)
+        C.roi_weights(d.data_ptr(), goff, desc.data_ptr(), buf.data_ptr() + doff, n, gt.data_ptr(), gt2.data_ptr(),
+                      ho, wo, downsample, tail[-1])
+        return x4, gt2
     return x4, gt
 
 
 def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = torch.bfloat16,
-                      copy_stream=None):
+                      copy_stream=None, roi: bool = False):
     """PackedCollate output -> (x4 [N,Ho,Wo,4] 16-bit NHWC4, gt [N,1,Ho/d,Wo/d] fp32): one copy of the packed buffer
     and one launch for the whole batch of images.  copy_stream: a torch.cuda.Stream the H2D copy is issued on (the
     compute stream then waits for it): a pinned copy queued behind the previous step's kernels on the compute stream
-    held the host ~0.6 ms per step at batch 1 (profiles/r5/host/), one on an idle copy stream does not."""
+    held the host ~0.6 ms per step at batch 1 (profiles/r5/host/), one on an idle copy stream does not.
+    roi=True (a CrowdDataset(roi=True) pack): returns (x4, gt2 [N,2,Ho/d,Wo/d]), the loss weights in channel 1."""
     C = _ext.require()
     buf, dims, kind = _unpack(packed)
     dev = torch.device(device)
@@ -282,7 +296,7 @@ def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = 
         d.record_stream(cur)              # allocated on the copy stream, consumed on the compute stream
     else:
         d = buf.to(dev, non_blocking=True)
-    return _launch(C, kind, buf, d, *dims, downsample, dtype, dev)
+    return _launch(C, kind, buf, d, *dims, downsample, dtype, dev, roi=roi)
 
 
 class AheadPrep:
@@ -295,7 +309,8 @@ class AheadPrep:
     nothing: with preprocess_packed(copy_stream=...) the kernel ran on the compute stream behind a wait for the copy.
     """
 
-    def __init__(self, device, dtype: torch.dtype = torch.bfloat16, downsample: int = 8):
+    def __init__(self, device, dtype: torch.dtype = torch.bfloat16, downsample: int = 8, roi: bool = False):
+        self.roi = bool(roi)                  # the packs carry ROI masks: gt comes back [n, 2, h, w] (_launch)
         self.device = torch.device(device)
         self.dtype = dtype
         self.ds = downsample
@@ -310,7 +325,7 @@ class AheadPrep:
         with torch.cuda.stream(self.copy):
             d = buf.to(self.device, non_blocking=True)
             with _ext.launch_on(self.copy.cuda_stream):
-                x4, gt = _launch(C, kind, buf, d, *dims, self.ds, self.dtype, self.device)
+                x4, gt = _launch(C, kind, buf, d, *dims, self.ds, self.dtype, self.device, roi=self.roi)
             ev = torch.cuda.Event()
             ev.record(self.copy)
         return x4, gt, d, ev
@@ -320,5 +335,7 @@ class AheadPrep:
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ev)
         x4.record_stream(cur)
-        d.record_stream(cur)                  # (gt is a view of d)
+        d.record_stream(cur)                  # (gt is a view of d, or with roi a tensor of its own)
+        if self.roi:
+            gt.record_stream(cur)
         return x4, gt

@@ -117,11 +117,21 @@ def crop_count(v):
     return n
 
 
+def game_level(v):
+    n = int(v)
+    if not 0 <= n <= 3:
+        raise argparse.ArgumentTypeError(f"--eval-game must be a level 0..3, got {v!r}")
+    return n
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
         if ns.crop_size is not None and ns.synthetic:
             self.error("--crop-size crops decoded dataset images; it cannot be combined with --synthetic")
+        if ns.roi_masks and ns.synthetic:
+            self.error("--roi-masks reads the dataset's ground_truth/NAME.roi.npy masks; it cannot be combined with "
+                       "--synthetic")
         if ns.crop_scale is not None and ns.crop_size is None:
             self.error("--crop-scale rescales the windows of --crop-size; give --crop-size as well")
         if ns.gt_from_heads and ns.crop_size is None:
@@ -210,7 +220,7 @@ def build_parser():
     p.add_argument("--crop-size", type=crop_size, default=None, metavar="HxW",
                    help="train on random HxW crops (multiples of 8) instead of whole images: any integer offset, a "
                         "p=0.5 flip per crop, an image smaller than the crop is zero-padded at the bottom / right "
-                        "(the padding takes part in the loss).  Every training batch then has one shape, so "
+                        "(the padding takes part in the loss, unless --roi-masks weights it out).  Every training batch then has one shape, so "
                         "--batch-size > 1 works on a mixed-size dataset; evaluation stays on whole images at batch 1.  "
                         "Default: off")
     p.add_argument("--crops-per-image", type=crop_count, default=1,
@@ -237,6 +247,14 @@ def build_parser():
     p.add_argument("--gray-prob", type=gray_prob, default=None, metavar="P",
                    help="with --crop-size: every crop is turned gray (luma 0.299 R + 0.587 G + 0.114 B in all three "
                         "channels, after the tone table of --photo-jitter) with this probability.  Default: off")
+    p.add_argument("--roi-masks", action="store_true",
+                   help="the dataset has a region-of-interest mask per image (ground_truth/NAME.roi.npy: uint8 [H, W], "
+                        "255 inside, 0 outside): the loss is weighted per cell by the mask's exact area mean (0 in the "
+                        "padding of a crop too), counts are taken inside the mask, and the epoch records gain rmse.  "
+                        "The weights are rendered on the GPU with --gpu-preprocess.  Default: off")
+    p.add_argument("--eval-game", type=game_level, default=None, metavar="L",
+                   help="evaluate with the grid average mean absolute error GAME(1..L) as well (0 <= L <= 3; GAME(0) "
+                        "is the MAE), logged as game1..gameL next to mae and rmse.  Default: off")
     p.add_argument("--log-every", type=int, default=20,
                    help="steps between the training records of --log-jsonl (each reads the loss back: a host sync)")
     return p
@@ -270,10 +288,11 @@ def make_loaders(args, world, rank, raw=False, device=None, dtype=None):
                                 gt_downsample=8, phase="train", seed=args.seed, raw=raw, crop=crop,
                                 crops_per_image=args.crops_per_image if crop is not None else 1,
                                 crop_scale=args.crop_scale, gt_from_heads=args.gt_from_heads,
+                                **(dict(roi=True) if args.roi_masks else {}),
                                 **(dict(photo_jitter=args.photo_jitter or (0.0, 0.0, 1.0),
                                         gray_prob=args.gray_prob or 0.0) if photo else {}))
         test_ds = CrowdDataset(os.path.join(r, "test_data", "images"), os.path.join(r, "test_data", "ground_truth"),
-                               gt_downsample=8, phase="test", raw=raw)
+                               gt_downsample=8, phase="test", raw=raw, **(dict(roi=True) if args.roi_masks else {}))
     train_sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed)
     test_sampler = DistributedSampler(test_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed)
     # indices carry the epoch into (persistent) workers: the flip is a function of (seed, epoch, index)
@@ -322,8 +341,9 @@ def main(args):
     if raw:
         from can_distributed_pytorch_amd.ops.preprocess import AheadPrep, preprocess_packed
         copy_stream = torch.cuda.Stream(device) if torch.device(device).type == "cuda" else None
-        prep = lambda b: preprocess_packed(b, device, dtype=act, copy_stream=copy_stream)  # noqa: E731
-        train_prep = AheadPrep(device, dtype=act)            # training: the next batch one step ahead
+        roi_kw = dict(roi=True) if args.roi_masks else {}    # the packs carry the masks as alpha: gt [n, 2, h, w]
+        prep = lambda b: preprocess_packed(b, device, dtype=act, copy_stream=copy_stream, **roi_kw)  # noqa: E731
+        train_prep = AheadPrep(device, dtype=act, **roi_kw)  # training: the next batch one step ahead
 
     model = CANNet(vgg16_path=args.vgg16 or None, backend="hip" if args.impl == "hip" else "torch",
                    batch_norm=args.batch_norm)
@@ -397,8 +417,20 @@ def main(args):
         t_train = time.perf_counter() - t0
         # EMA on: evaluation, the overlay PNGs and the best-MAE checkpoint see the averaged weights (every rank swaps)
         averaged = stepper.ema_weights if ema_on else contextlib.nullcontext
+        metrics_on = args.roi_masks or args.eval_game is not None
+        extra = {}
         with averaged():
-            if (epoch + 1) % args.eval_every == 0 or epoch == args.epochs - 1:
+            evaluating = (epoch + 1) % args.eval_every == 0 or epoch == args.epochs - 1
+            if evaluating and metrics_on:
+                # masked counts, RMSE and GAME (engine/metrics.py): sums over the test set, one collective; the best
+                # checkpoint is chosen by the masked MAE, GAME_0's mean
+                from can_distributed_pytorch_amd.engine.metrics import evaluate_metrics
+                ms = evaluate_metrics(net, test_loader, device, prep=prep)
+                mae_sum = ms["game"][0]
+                extra = dict(rmse=math.sqrt(ms["se"] / test_sampler.total_size),
+                             **{f"game{l}": ms["game"][l] / test_sampler.total_size
+                                for l in range(1, (args.eval_game or 0) + 1)})
+            elif evaluating:
                 mae_sum = evaluate(net, test_loader, device, epoch, show_images=args.show and rank == 0,
                                    use_wandb=use_wandb, out_dir=os.path.join(args.checkpoint_dir, "temp"), prep=prep)
             else:
@@ -440,7 +472,8 @@ def main(args):
                     **(dict(gt_from_heads=True) if args.gt_from_heads else {}),
                     **(dict(photo_jitter=list(args.photo_jitter)) if args.photo_jitter is not None else {}),
                     **(dict(gray_prob=args.gray_prob) if args.gray_prob is not None else {}),
-                    **(dict(ema_decay=args.ema_decay) if ema_on else {}))
+                    **(dict(ema_decay=args.ema_decay) if ema_on else {}),
+                    **(dict(roi_masks=True) if args.roi_masks else {}), **extra)
             if use_wandb:
                 wandb_log(loss=mean_loss, mae=mean_mae, lr=lr_now)
         barrier()
