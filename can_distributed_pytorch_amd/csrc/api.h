@@ -16,9 +16,10 @@ int can_conv_igemm(const void* x, const void* w, const float* bias, const void* 
 
 int can_wgrad_plan(int M, int Cin, int Cout, int ksize, int first, int target_blocks, int* S_out, int* mslice_out,
                    int* cfg_out, int dil, int W);
-int can_conv_wgrad(const void* dy, const void* x, float* ws, float* wsb, float* dw, float* db, int N, int H, int W,
-                   int Cin, int Cout, int ksize, int dil, int first, int S, int mslice, int cfg, float beta,
-                   float scale, const float* dscale, int dt, void* stream, const float* bext, int bext_rows);
+// the weight-gradient launchers plan their launch themselves (wgrad_plan.h); ws_floats: the size of ws
+int can_conv_wgrad(const void* dy, const void* x, float* ws, long long ws_floats, float* dw, float* db, int N, int H,
+                   int W, int Cin, int Cout, int ksize, int dil, int first, float beta, float scale,
+                   const float* dscale, int dt, void* stream, const float* bext, int bext_rows);
 // stream events from one ring: record on a stream (returns the slot, < 0 error), wait for a slot, or both
 int can_event_record(void* stream);
 int can_event_wait(void* stream, int slot);
@@ -26,9 +27,9 @@ int can_stream_wait(void* dst, void* src);
 
 // [R][C] fp32 rows -> <= rows_out rows (fixed-order block sums); returns the rows written (< 0: error)
 int can_bias_rows_reduce(const float* in, float* out, int R, int C, int rows_out, void* stream);
-int can_conv_wgrad_1x1_batched(const void* dy, const void* x, float* ws, float* dw, int M, int W, int Cin, int Cout,
-                               int nb, long long dy_bs, long long x_bs, long long dw_bs, int S, int mslice, float beta,
-                               float scale, const float* dscale, int dt, void* stream);
+int can_conv_wgrad_1x1_batched(const void* dy, const void* x, float* ws, long long ws_floats, float* dw, int M, int W,
+                               int Cin, int Cout, int nb, long long dy_bs, long long x_bs, long long dw_bs, int ncu,
+                               float beta, float scale, const float* dscale, int dt, void* stream);
 
 // conv + bias + ReLU with the 2x2/s2 max-pool fused into the epilogue (y full resolution, yp pooled)
 // codes: max-pool codes uint32 [N][H/2][W/2][Cout/8] (optional), y optional (nullptr: not written)

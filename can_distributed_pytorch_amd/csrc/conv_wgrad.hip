@@ -30,6 +30,7 @@
 #include "api.h"
 #include "common.h"
 #include "fastdiv.h"
+#include "wgrad_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -524,20 +525,22 @@ __global__ void __launch_bounds__(64 * WC * WK * WM, (WC * WK * WM >= 8) ? 1 : 2
   }
 }
 
-template <int DT, int WC, int WK, int WM, int NBUF, int KW, int KK>
-static int launch_wgrad2(const WgradArgs2& a, hipStream_t s) {
-  constexpr int NW = WC * WK * WM;
-  constexpr int STAGE = 32 * KK * WM * (64 * WC + 64 * WK * KW) * 2;
-  size_t lds = (size_t)NBUF * STAGE;
-  if (WM > 1) lds = std::max(lds, (size_t)(NW * 16 * 64 * 4 + NW * 4 * 64 * 4) * 4);
-  auto kfn = wgrad_glds_kernel<DT, WC, WK, WM, NBUF, KW, KK>;
+// CFG: a WG_GLDS row of kWgradTiles (the kernel's template arguments); blocks: the plan's tiles x slices
+template <int DT, int CFG>
+static int launch_wgrad2(const WgradArgs2& a, int blocks, hipStream_t s) {
+  constexpr WgradTile t = *find_wgrad_tile(CFG);
+  static_assert(t.fam == WG_GLDS, "not a v1 config");
+  constexpr int NW = t.WC * t.WK * t.WM;
+  constexpr int STAGE = t.BKM * (t.TCo + t.TK) * 2;
+  size_t lds = (size_t)t.NBUF * STAGE;
+  if (t.WM > 1) lds = std::max(lds, (size_t)(NW * 16 * 64 * 4 + NW * 4 * 64 * 4) * 4);
+  auto kfn = wgrad_glds_kernel<DT, t.WC, t.WK, t.WM, t.NBUF, t.KW, t.KK>;
   static bool attr = false;
   if (!attr) {
     CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  const int ntile = (a.Cout / (64 * WC)) * ((a.K + 64 * WK * KW - 1) / (64 * WK * KW));
-  hipLaunchKernelGGL(kfn, dim3(ntile * a.S), dim3(64 * NW), lds, s, a);
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64 * NW), lds, s, a);
   return (int)hipGetLastError();
 }
 
@@ -836,18 +839,20 @@ __global__ void __launch_bounds__(256) bias_colsum_kernel(const bf16_t* __restri
   }
 }
 
-template <int DT, int WC, int WK, int KW, bool RW = false>
-static int launch_wgrad3(const WgradArgs2& a, hipStream_t s) {
-  constexpr int STAGE = 64 * (64 * WC + 64 * WK * KW) * 2;
+// CFG: a WG_GLDS2 row of kWgradTiles; blocks: the plan's tiles x slices (x items of a batched launch)
+template <int DT, int CFG, bool RW = false>
+static int launch_wgrad3(const WgradArgs2& a, int blocks, hipStream_t s) {
+  constexpr WgradTile t = *find_wgrad_tile(CFG);
+  static_assert(t.fam == WG_GLDS2, "not a v2 config");
+  constexpr int STAGE = t.BKM * (t.TCo + t.TK) * 2;
   const size_t lds = 2 * (size_t)STAGE;
-  auto kfn = wgrad_glds2_kernel<DT, WC, WK, KW, RW>;
+  auto kfn = wgrad_glds2_kernel<DT, t.WC, t.WK, t.KW, RW>;
   static bool attr = false;
   if (!attr) {
     CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  const int ntile = (a.Cout / (64 * WC)) * (a.K / (64 * WK * KW));
-  hipLaunchKernelGGL(kfn, dim3(ntile * a.S * a.nb), dim3(64 * WC * WK), lds, s, a);
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(64 * t.WC * t.WK), lds, s, a);
   return (int)hipGetLastError();
 }
 
@@ -878,31 +883,22 @@ struct HaloArgs {
 
 #include "wgrad_ring.inc"
 
-template <int DT, int WC, int WK, int WM, bool FIRST>
-static int launch_wgrad(const WgradArgs& a, hipStream_t s) {
-  constexpr int TCo = 64 * WC, TK = 64 * WK;
-  constexpr int KSUB = (WM == 1) ? 2 : 1;
-  constexpr int BKM = 32 * KSUB * WM;
-  size_t lds = 2 * BKM * (TCo + TK) * 2;
-  if (WM != 1) lds = std::max(lds, (size_t)(4 * 16 * 64 * 4 + 4 * 4 * 64 * 4) * 4);
-  auto kfn = conv_wgrad_kernel<DT, WC, WK, WM, FIRST>;
+// the first layer: cfg 0 of kWgradTiles (four waves splitting each stage's pixels)
+template <int DT>
+static int launch_wgrad_first(const WgradArgs& a, int blocks, hipStream_t s) {
+  constexpr WgradTile t = *find_wgrad_tile(0);
+  static_assert(t.fam == WG_FIRST && t.WM == 4, "cfg 0 is the pixel-split first-layer kernel");
+  const size_t lds = std::max<size_t>(2 * t.BKM * (t.TCo + t.TK) * 2, (4 * 16 * 64 * 4 + 4 * 4 * 64 * 4) * 4);
+  auto kfn = conv_wgrad_kernel<DT, t.WC, t.WK, t.WM, true>;
   static bool attr = false;
   if (!attr) {
     CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  const int ntile = (a.Cout / TCo) * (a.Ktot / TK);
-  hipLaunchKernelGGL(kfn, dim3(ntile * a.S), dim3(256), lds, s, a);
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, s, a);
   return (int)hipGetLastError();
 }
 
-}  // namespace can
-
-// Tile configs of the pipelined kernel: 1 = 128co x 128k (4 waves, 4 bufs),
-// 2 = 256co x 128k (8 waves, 3 bufs), 3 = 64co x 128k (4 waves, pixel-split 2,
-// 3 bufs), 4 = 64co x 64k (2 waves, pixel-split 2, 4 bufs); 0 = first layer
-// (register-staged kernel).
-namespace can {
 // Sum S slabs [S][K][Cout] in a fixed order and write dW in the PyTorch layout
 // [Cout][Cin][kh][kw] (first layer: Cin = 3 real channels of the k = tap*4 + c
 // packing); beta = 0 overwrites, 1 accumulates.
@@ -996,8 +992,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce2_kernel(const float* __restr
 // Tiled form for 3x3 layers with few slabs (S <= 16): block = 64 output channels x RCI input channels x 9 taps.
 // Slab rows (tap, ci) are read as 256-B runs of 64 co, summed over the slabs in order, transposed through LDS
 // and written as 64 contiguous runs of RCI*9 floats of dW[co][ci][tap] (the grid-stride form writes dW with a
-// Cin*9-float stride between neighbouring lanes: one 4-B store per 64-B line).
-constexpr int RCI = 8;
+// Cin*9-float stride between neighbouring lanes: one 4-B store per 64-B line).  RCI: wgrad_plan.h
 __global__ void __launch_bounds__(256) wgrad_reduce_tiled_kernel(const float* __restrict__ ws,
                                                                  const float* __restrict__ wsb,
                                                                  float* __restrict__ dw, float* __restrict__ db,
@@ -1086,127 +1081,43 @@ static int launch_reduce2(const float* ws, const float* wsb, float* dw, float* d
                           int Cin, int taps, int first, float beta, float scale, const float* dscale, hipStream_t s) {
   const size_t plane = (size_t)K * Cout;
   const int nbias = (db != nullptr) ? (Cout + 15) / 16 : 0;
-  auto grid = [&](int epb) { return (int)std::min<size_t>((plane + epb - 1) / epb, 4096) + nbias; };
-  if (!first && taps == 9 && S <= 16 && Cout % 64 == 0 && Cin % RCI == 0 &&
-      (Cout / 64) * (Cin / RCI) >= 256) {
-    hipLaunchKernelGGL(wgrad_reduce_tiled_kernel, dim3((Cout / 64) * (Cin / RCI) + nbias), dim3(256), 0, s, ws, wsb,
-                       dw, db, S, Sb, Cout, Cin, beta, scale, dscale);
-  } else if (S <= 16)
-    hipLaunchKernelGGL(wgrad_reduce2_kernel<1>, dim3(grid(256)), dim3(256), 0, s, ws, wsb, dw, db, S, Sb, K, Cout,
-                       Cin, taps, first, beta, scale, dscale);
-  else if (S <= 128)
-    hipLaunchKernelGGL(wgrad_reduce2_kernel<4>, dim3(grid(64)), dim3(256), 0, s, ws, wsb, dw, db, S, Sb, K, Cout,
-                       Cin, taps, first, beta, scale, dscale);
-  else if (plane < 4096)
-    // a small plane over many slabs (conv1_1's 36 x 64 over the ~512 slabs of the fused w1g kernel): 64 slab groups
-    // of 4 elements per block, 8 slabs per thread -- <16> gave 148 blocks of 32 dependent loads per thread, 37 us
-    hipLaunchKernelGGL(wgrad_reduce2_kernel<64>, dim3(grid(4)), dim3(256), 0, s, ws, wsb, dw, db, S, Sb, K, Cout,
-                       Cin, taps, first, beta, scale, dscale);
-  else
-    hipLaunchKernelGGL(wgrad_reduce2_kernel<16>, dim3(grid(16)), dim3(256), 0, s, ws, wsb, dw, db, S, Sb, K, Cout,
-                       Cin, taps, first, beta, scale, dscale);
+  auto grid = [&](int epb) { return dim3((int)std::min<size_t>((plane + epb - 1) / epb, 4096) + nbias); };
+#define CAN_REDUCE2(SG)                                                                                              \
+  hipLaunchKernelGGL(wgrad_reduce2_kernel<SG>, grid(256 / SG), dim3(256), 0, s, ws, wsb, dw, db, S, Sb, K, Cout, Cin, \
+                     taps, first, beta, scale, dscale)
+  switch (wgrad_reduce_kind(S, K, Cout, Cin, taps, first)) {
+    case RED_TILED:
+      hipLaunchKernelGGL(wgrad_reduce_tiled_kernel, dim3((Cout / 64) * (Cin / RCI) + nbias), dim3(256), 0, s, ws, wsb,
+                         dw, db, S, Sb, Cout, Cin, beta, scale, dscale);
+      break;
+    case RED_1: CAN_REDUCE2(1); break;
+    case RED_4: CAN_REDUCE2(4); break;
+    case RED_64: CAN_REDUCE2(64); break;
+    default: CAN_REDUCE2(16); break;
+  }
+#undef CAN_REDUCE2
   return (int)hipGetLastError();
 }
 }  // namespace can
 using namespace can;
 
-// bias partial count of the v2 path (workspace: max(S, kBiasParts) x Cout floats)
-static constexpr int kBiasParts = 512;
-
-static void wgrad_tile(int cfg, int* TCo, int* TK, int* BKM) {
-  switch (cfg) {
-    case 1: *TCo = 128; *TK = 128; *BKM = 64; break;
-    case 2: *TCo = 256; *TK = 128; *BKM = 64; break;
-    case 3: *TCo = 64; *TK = 128; *BKM = 128; break;
-    case 4: *TCo = 64; *TK = 64; *BKM = 128; break;
-    case 5: *TCo = 256; *TK = 256; *BKM = 32; break;
-    case 6: *TCo = 128; *TK = 256; *BKM = 64; break;
-    case 7: *TCo = 256; *TK = 256; *BKM = 64; break;
-    case 9: *TCo = 256; *TK = 256; *BKM = 64; break;   // v2 (row-aligned layers), falls back to 7
-    case 10: *TCo = 256; *TK = 128; *BKM = 64; break;  // v2 256co x 128k (Cin = 128), falls back to 2
-    case 11: *TCo = 128; *TK = 256; *BKM = 64; break;  // v2 128co x 256k (Cout = 128), falls back to 6
-    case 8: *TCo = 0; *TK = 0; *BKM = 128; break;   // halo kernel: tiles of 2x64 pixels
-    default: *TCo = 64; *TK = 64; *BKM = 128; break;
-  }
+static WgradQuery wgrad_query(int N, int H, int W, int Cin, int Cout, int ksize, int dil, int first) {
+  WgradQuery q;
+  q.N = N; q.H = H; q.W = W; q.M = N * H * W; q.Cin = Cin; q.Cout = Cout; q.ksize = ksize; q.dil = dil; q.first = first;
+  return q;
 }
 
+// S, mslice and cfg of the launch plan for M pixels in rows of W (0, or no divisor of M: width unknown; the image
+// height is not known here).  A first layer is planned whatever Cin says (its packed input always has 4 channels).
 extern "C" int can_wgrad_plan(int M, int Cin, int Cout, int ksize, int first, int target_blocks, int* S_out,
                               int* mslice_out, int* cfg_out, int dil, int W) {
-  const int K = first ? 64 : ksize * ksize * Cin;
-  int cfg;
-  // the halo weight-gradient kernel is dilation-1 only (B5: 256 -> 128, dil 2, reaches M >= 262144 at batch 32)
-  const bool halo_ok = !first && ksize == 3 && dil == 1 && (Cout == 64 || Cout == 128) && Cin % 64 == 0;
-  if (first) cfg = 0;
-  else if (halo_ok && M >= 262144) cfg = 8;
-  else if (Cout % 256 == 0 && K >= 2048) cfg = (K % 256 == 0) ? 9 : 7;
-  else if (Cout % 256 == 0 && ksize == 1 && K % 256 == 0 && K >= 512)
-    cfg = 9;   // 1x1 with many output rows (the linearised context module's dW2cat: 2048 x 512)
-  else if (Cout % 256 == 0 && K >= 1024)
-    cfg = (Cin % 128 == 0) ? 10 : 2;
-  else if (Cout == 128 && Cin % 256 == 0 && K >= 2048)
-    cfg = 11;
-  else if (Cout % 128 == 0 && K >= 2048) cfg = 6;
-  else if (Cout % 128 == 0) cfg = 1;
-  else if (K >= 128) cfg = 3;
-  else cfg = 4;
-  // the tap-ring kernel (wgrad_tap.inc) for the layers the v2 GEMM takes (dispatch wgrad_tap >= 1) and the Cout = 128
-  // ones of the full-resolution ring kernel (>= 2); it needs the map width (W = 0: unknown, not chosen)
-  int ncu = can_device_cus();
-  if (ncu <= 0) ncu = 256;                         // no device (host-only planning): an MI355X's count
-  // the smallest slice count that fills whole rounds of one-block-per-CU launches to >= 90 %
-  auto whole_rounds = [&](int ntile) {
-    for (int R = 1; R <= 8; ++R) {
-      const int s = (ncu * R) / ntile;
-      if (s >= 1 && (long long)ntile * s * 10 >= 9LL * ncu * R) return s;
-    }
-    return 0;
-  };
-  const int tco = wgrad_tap_tco(Cout);
-  if (!first && W > 0 && M % W == 0 && wgrad_tap_ok(1, M / W, W, Cin, Cout, ksize, dil) && cfg != 0 &&
-      g_dispatch.wgrad_tap >= (tco == 64 ? 3 : cfg == 8 ? 2 : 1)) {
-    // one block per CU (TCO 128) or two (TCO 64)
-    const int ntile = (Cin / 64) * (Cout / tco);
-    const int stages = (M / W) * ((W + 63) / 64);
-    const int slots_per_cu = (tco == 128) ? 1 : 2;
-    int S = 0;
-    for (int R = 1; R <= 8 && !S; ++R) {
-      const int s = (ncu * slots_per_cu * R) / ntile;
-      if (s >= 1 && (long long)ntile * s * 10 >= 9LL * ncu * slots_per_cu * R) S = s;
-    }
-    if (S < 1) S = max(1, ncu * slots_per_cu / ntile);
-    if (S > stages) S = stages;
-    *S_out = S; *mslice_out = 0; *cfg_out = 12;
-    return 0;
-  }
-  int TCo, TK, BKM;
-  wgrad_tile(cfg, &TCo, &TK, &BKM);
-  if (cfg == 8) {
-    // slices of whole 2x64-pixel tiles; the Python side passes N,H,W to the launcher,
-    // here only the slice count matters: ~2 blocks per CU worth of (ci tile, slice) pairs.
-    const int nci = (Cin / 64) * (Cout / 64);
-    int S = 512 / nci;
-    if (S < 1) S = 1;
-    *S_out = S; *mslice_out = 0; *cfg_out = cfg;
-    return 0;
-  }
-  const int ntile = (Cout / TCo) * ((K + TK - 1) / TK);
-  // whole rounds of co-resident blocks (no half-empty last round)
-  int S = target_blocks / ntile;
-  if (cfg != 0 && cfg != 8) {
-    // the pipelined kernels run one block per CU (LDS ring >= 128 KB): as few pixel slices as fill
-    // whole rounds of the CUs to >= 90 % (fewer fp32 partial slabs to write and
-    // reduce, longer K loops per block)
-    const int wr = whole_rounds(ntile);
-    if (wr) S = wr;
-  }
-  if (S < 1) S = 1;
-  const int max_s = (M + BKM - 1) / BKM;
-  if (S > max_s) S = max_s;
-  if (S < 1) S = 1;
-  int mslice = (M + S - 1) / S;
-  mslice = ((mslice + BKM - 1) / BKM) * BKM;
-  S = (M + mslice - 1) / mslice;
-  *S_out = S; *mslice_out = mslice; *cfg_out = cfg;
+  if (W <= 0 || M % W) W = 0;
+  WgradQuery q = wgrad_query(1, 0, W, first ? 4 : Cin, Cout, ksize, dil, first);
+  q.M = M;
+  q.target_blocks = target_blocks;
+  const WgradPlan p = plan_wgrad(q, g_dispatch, can_device_cus());
+  if (p.err) return p.err;
+  *S_out = p.S; *mslice_out = p.mslice; *cfg_out = p.cfg;
   return 0;
 }
 
@@ -1253,163 +1164,79 @@ extern "C" int can_stream_wait(void* dst, void* src) {
   return k < 0 ? k : can_event_wait(dst, k);
 }
 
+// Executes plan p (wgrad_plan.h): the bias column sums (WB_COLSUM), the planned kernel, the fold of a long external
+// bias list (WB_EXT_FOLD), the slab reduction.
 template <int DT>
-static int conv_wgrad_impl(const void* dy, const void* x, float* ws, float* wsb, float* dw, float* db, int N, int H,
-                           int W, int Cin, int Cout, int ksize, int dil, int first, int S, int mslice, int cfg,
-                           float beta, float scale, const float* dscale, void* stream, const float* bext,
-                           int bext_rows) {
-  using namespace can;
-  hipStream_t s = (hipStream_t)stream;
-  hipStream_t rs = s;
-  const int K = first ? 64 : ksize * ksize * Cin;
-  if ((long long)K * Cout >= 0x7fffffffLL) return -9;   // 32-bit plane indexing in the reduction
-  // external bias partials (the dgrad epilogue that produced dY summed it): no bias work in the GEMM /
-  // column-sum kernels, only a rows pre-reduction into the workspace's bias area (<= kBiasParts rows)
-  const bool ext = (db != nullptr) && (bext != nullptr) && bext_rows > 0;
-  if (ext && (Cout % 64 || Cout > 1024)) return -15;
-  float* wsb_used = (db != nullptr && !ext) ? wsb : nullptr;
-  int rc;
-  int Sb = S;                       // bias partials summed by the reduce kernel
-  int Sb_ext = 0;
-  const float* bsrc = wsb;          // bias partial rows the reduce kernel sums (external: bext itself when short)
-  // long external lists are folded to <= kBiasParts rows by a short launch queued AFTER the GEMM on this (weight-
-  // gradient) stream: it then takes the CUs the GEMM's last blocks release.  Queued on the data-gradient stream (the
-  // producer) it waited 85-345 us for CUs behind this stream's one-block-per-CU GEMM, on the critical path
-  // (profiles/r3/ab_bias_prereduce.txt)
-  int bias_rpb = 0;
-  if (ext) {
-    if (bext_rows <= kBiasParts) {
-      bsrc = bext;
-      Sb_ext = bext_rows;
-    } else {
-      bias_rpb = (bext_rows + kBiasParts - 1) / kBiasParts;
-      Sb_ext = (bext_rows + bias_rpb - 1) / bias_rpb;
-    }
-  }
-  auto bias_pre = [&]() {
-    if (bias_rpb)
-      hipLaunchKernelGGL(bias_rows_reduce_kernel, dim3(Sb_ext), dim3(256), 0, rs, bext, wsb, bext_rows, Cout, bias_rpb);
-  };
-  if (first || cfg == 0) {
-    if (Cin != 4 || Cout % 64) return -2;
+static int conv_wgrad_impl(const void* dy, const void* x, float* ws, float* dw, float* db, int N, int H, int W,
+                           int Cin, int Cout, int ksize, int dil, float beta, float scale, const float* dscale,
+                           hipStream_t s, const float* bext, int bext_rows, const WgradPlan& p) {
+  const int first = p.fam == WG_FIRST, K = first ? 64 : ksize * ksize * Cin, M = N * H * W, S = p.S;
+  float* wsb = ws + p.bias_off;
+  float* wsb_k = (p.bias == WB_KERNEL) ? wsb : nullptr;    // partial rows the GEMM / halo kernel writes itself
+  const bf16_t* zero = first ? nullptr : (const bf16_t*)can_zero_page();
+  if (!first && !zero) return -7;
+  if (p.bias == WB_COLSUM)
+    hipLaunchKernelGGL(bias_colsum_kernel<DT>, dim3(p.Sb), dim3(256), 0, s, (const bf16_t*)dy, wsb, M, Cout, p.Sb);
+  int rc = -5;
+  if (p.fam == WG_FIRST) {
     WgradArgs a;
-    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.ws = ws; a.wsb = wsb_used;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = ksize; a.dil = dil; a.M = N * H * W;
-    a.Ktot = 64; a.S = S; a.mslice = mslice;
-    rc = launch_wgrad<DT, 1, 1, 4, true>(a, s);
+    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.ws = ws; a.wsb = wsb_k;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = ksize; a.dil = dil; a.M = M;
+    a.Ktot = 64; a.S = S; a.mslice = p.mslice;
+    rc = launch_wgrad_first<DT>(a, p.blocks, s);
+  } else if (p.fam == WG_TAP) {
+    TapArgs t;
+    t.dy = (const bf16_t*)dy; t.x = (const bf16_t*)x; t.ws = ws;
+    t.N = N; t.H = H; t.W = W; t.Cin = Cin; t.Cout = Cout;
+    t.tx64 = (W + 63) / 64;
+    t.total = p.tap_total;
+    t.S = S;
+    t.spb = p.tap_spb;
+    t.dy_bytes = (unsigned)((long long)M * Cout * 2);
+    t.x_bytes = (unsigned)((long long)M * Cin * 2);
+    // double-buffered dY fragments (step +0.45 %, profiles/r4/ab_wgrad_tap_variants.txt)
+    if (wgrad_tap_tco(Cout) == 128)
+      rc = (dil == 1) ? launch_wgrad_tap<DT, 1, 128, true>(t, s) : launch_wgrad_tap<DT, 2, 128, true>(t, s);
+    else
+      rc = (dil == 1) ? launch_wgrad_tap<DT, 1, 64, true>(t, s) : launch_wgrad_tap<DT, 2, 64, true>(t, s);
+  } else if (p.fam == WG_HALO) {
+    HaloArgs h;
+    h.dy = (const bf16_t*)dy; h.x = (const bf16_t*)x; h.zero = zero; h.ws = ws; h.wsb = wsb_k;
+    h.N = N; h.H = H; h.W = W; h.Cin = Cin; h.Cout = Cout; h.K = K; h.S = S;
+    h.tiles_y = (H + 3) / 4; h.tiles_x = (W + 63) / 64; h.ntiles = p.halo_tiles;
+    h.tiles_per_slice = p.halo_tps;
+    rc = launch_halo_ring<DT, 64, 4>(h, s);
   } else {
-    if (Cin % 64 || Cout % 64 || ((H < 2 || W < 2) && cfg != 12)) return -3;
+    const bool v2 = p.fam == WG_GLDS2;
     WgradArgs2 a;
-    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.zero = (const bf16_t*)can_zero_page(); a.ws = ws; a.wsb = wsb_used;
-    if (!a.zero) return -7;
-    a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = ksize; a.dil = dil; a.M = N * H * W; a.K = K;
-    a.S = S; a.mslice = mslice;
+    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.zero = zero; a.ws = ws; a.wsb = wsb_k;
+    a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksize = ksize; a.dil = dil; a.K = K; a.S = S;
+    a.M = v2 ? p.vM : M; a.mslice = v2 ? p.vmslice : p.mslice; a.Mreal = M;
     a.fdW = make_fastdiv((uint32_t)W); a.fdH = make_fastdiv((uint32_t)H); a.fdC = make_fastdiv((uint32_t)Cin);
-    a.Mreal = a.M;
     a.tx64 = (W + 63) / 64; a.fdTX = make_fastdiv((uint32_t)a.tx64);
-    // v2 on a ragged width: virtual pixels (every row padded to whole 64-pixel stages), the same slice count
-    const bool rw = (W % 64) != 0 && ksize == 3;
-    WgradArgs2 gv = a;
-    if (rw) {
-      gv.M = N * H * a.tx64 * 64;
-      gv.mslice = ((gv.M + S - 1) / S + 63) / 64 * 64;   // slices past the end run no stage and write zero slabs
-    }
-    if (cfg == 12) {
-      if (!wgrad_tap_ok(N, H, W, Cin, Cout, ksize, dil)) return -6;
-      if (wsb_used) {
-        Sb = kBiasParts;
-        hipLaunchKernelGGL(bias_colsum_kernel<DT>, dim3(Sb), dim3(256), 0, s, a.dy, wsb_used, a.M, Cout, Sb);
-      }
-      TapArgs t;
-      t.dy = a.dy; t.x = a.x; t.ws = ws;
-      t.N = N; t.H = H; t.W = W; t.Cin = Cin; t.Cout = Cout;
-      t.tx64 = (W + 63) / 64;
-      t.total = N * H * t.tx64;
-      t.S = S;
-      t.spb = (t.total + S - 1) / S;
-      t.dy_bytes = (unsigned)((long long)a.M * Cout * 2);
-      t.x_bytes = (unsigned)((long long)a.M * Cin * 2);
-      // double-buffered dY fragments (step +0.45 %, profiles/r4/ab_wgrad_tap_variants.txt)
-      if (wgrad_tap_tco(Cout) == 128)
-        rc = (dil == 1) ? launch_wgrad_tap<DT, 1, 128, true>(t, s) : launch_wgrad_tap<DT, 2, 128, true>(t, s);
-      else
-        rc = (dil == 1) ? launch_wgrad_tap<DT, 1, 64, true>(t, s) : launch_wgrad_tap<DT, 2, 64, true>(t, s);
-      if (rc) return rc;
-      bias_pre();
-      return ext ? launch_reduce2(ws, bsrc, dw, db, S, Sb_ext, K, Cout, Cin, 9, 0, beta, scale, dscale, rs)
-                 : launch_reduce2(ws, wsb_used, dw, db, S, Sb, K, Cout, Cin, 9, 0, beta, scale, dscale, rs);
-    }
-    if (cfg == 8) {
-      if (ksize != 3 || dil != 1 || (Cout != 64 && Cout != 128) || Cin % 64) return -6;
-      HaloArgs h;
-      h.dy = a.dy; h.x = a.x; h.zero = a.zero; h.ws = ws; h.wsb = wsb_used;
-      h.N = N; h.H = H; h.W = W; h.Cin = Cin; h.Cout = Cout; h.K = K; h.S = S;
-      // Cout = 128 runs as two 64-channel co tiles: the row-ring kernel (4-row tiles walked down 64-column strips,
-      // each input row fetched once per strip)
-      h.tiles_y = (H + 3) / 4; h.tiles_x = (W + 63) / 64; h.ntiles = N * h.tiles_y * h.tiles_x;
-      h.tiles_per_slice = (h.ntiles + S - 1) / S;
-      rc = launch_halo_ring<DT, 64, 4>(h, s);
-      if (rc) return rc;
-      bias_pre();
-      return ext ? launch_reduce2(ws, bsrc, dw, db, S, Sb_ext, K, Cout, Cin, 9, 0, beta, scale, dscale, rs)
-                 : launch_reduce2(ws, wsb_used, dw, db, S, S, K, Cout, Cin, 9, 0, beta, scale, dscale, rs);
-    }
-    switch (cfg) {
-      case 1: if (Cout % 128) return -4; rc = launch_wgrad2<DT, 2, 2, 1, 4, 1, 2>(a, s); break;
-      case 2: if (Cout % 256) return -4; rc = launch_wgrad2<DT, 4, 2, 1, 3, 1, 2>(a, s); break;
-      case 3: rc = launch_wgrad2<DT, 1, 2, 2, 3, 1, 2>(a, s); break;
-      case 4: rc = launch_wgrad2<DT, 1, 1, 2, 4, 1, 2>(a, s); break;
-      case 5: if (Cout % 256) return -4; rc = launch_wgrad2<DT, 4, 2, 1, 4, 2, 1>(a, s); break;
-      case 6: if (Cout % 128) return -4; rc = launch_wgrad2<DT, 2, 2, 1, 3, 2, 2>(a, s); break;
-      case 7: if (Cout % 256) return -4; rc = launch_wgrad2<DT, 4, 2, 1, 2, 2, 2>(a, s); break;
-      case 9:
-        if (Cout % 256) return -4;
-        if ((W % 64 == 0 || rw) && Cin % 256 == 0 && gv.mslice % 64 == 0 && (long long)a.M * Cout * 2 < 0x7fffffffLL &&
-            Cout <= 2048) {
-          if (wsb_used) {
-            Sb = kBiasParts;
-            hipLaunchKernelGGL(bias_colsum_kernel<DT>, dim3(Sb), dim3(256), 0, s, a.dy, wsb_used, a.M, Cout, Sb);
-          }
-          WgradArgs2 g = gv;
-          g.wsb = nullptr;
-          rc = rw ? launch_wgrad3<DT, 4, 2, 2, true>(g, s) : launch_wgrad3<DT, 4, 2, 2>(g, s);
-        } else
-          rc = launch_wgrad2<DT, 4, 2, 1, 2, 2, 2>(a, s);   // same tiles / slicing as cfg 7
-        break;
-      case 10:   // 256co x 128k v2 (k tile = one tap of a Cin % 128 layer); fallback = cfg 2 tiles
-      case 11: { // 128co x 256k v2 (Cout = 128); fallback = cfg 6 tiles
-        const int tk = (cfg == 10) ? 128 : 256;
-        if (Cout % (cfg == 10 ? 256 : 128)) return -4;
-        if ((W % 64 == 0 || rw) && Cin % tk == 0 && K % tk == 0 && gv.mslice % 64 == 0 &&
-            (long long)a.M * Cout * 2 < 0x7fffffffLL && Cout <= 2048) {
-          if (wsb_used) {
-            Sb = kBiasParts;
-            hipLaunchKernelGGL(bias_colsum_kernel<DT>, dim3(Sb), dim3(256), 0, s, a.dy, wsb_used, a.M, Cout, Sb);
-          }
-          WgradArgs2 g = gv;
-          g.wsb = nullptr;
-          if (rw) rc = (cfg == 10) ? launch_wgrad3<DT, 4, 2, 1, true>(g, s) : launch_wgrad3<DT, 2, 4, 1, true>(g, s);
-          else rc = (cfg == 10) ? launch_wgrad3<DT, 4, 2, 1>(g, s) : launch_wgrad3<DT, 2, 4, 1>(g, s);
-        } else {
-          rc = (cfg == 10) ? launch_wgrad2<DT, 4, 2, 1, 3, 1, 2>(a, s) : launch_wgrad2<DT, 2, 2, 1, 3, 2, 2>(a, s);
-        }
-        break;
-      }
-      default: return -5;
+    // a cfg 9 / 10 / 11 layer the v2 kernel cannot take runs the v1 config of the same tiles
+    const int v1 = find_wgrad_tile(p.cfg)->v1;
+    switch ((v2 || !v1) ? p.cfg : v1) {
+      case 1: rc = launch_wgrad2<DT, 1>(a, p.blocks, s); break;
+      case 2: rc = launch_wgrad2<DT, 2>(a, p.blocks, s); break;
+      case 3: rc = launch_wgrad2<DT, 3>(a, p.blocks, s); break;
+      case 4: rc = launch_wgrad2<DT, 4>(a, p.blocks, s); break;
+      case 6: rc = launch_wgrad2<DT, 6>(a, p.blocks, s); break;
+      case 7: rc = launch_wgrad2<DT, 7>(a, p.blocks, s); break;
+      case 9: rc = p.ragged ? launch_wgrad3<DT, 9, true>(a, p.blocks, s) : launch_wgrad3<DT, 9>(a, p.blocks, s); break;
+      case 10: rc = p.ragged ? launch_wgrad3<DT, 10, true>(a, p.blocks, s) : launch_wgrad3<DT, 10>(a, p.blocks, s); break;
+      case 11: rc = p.ragged ? launch_wgrad3<DT, 11, true>(a, p.blocks, s) : launch_wgrad3<DT, 11>(a, p.blocks, s); break;
     }
   }
   if (rc) return rc;
-  bias_pre();
-  if (ext) return launch_reduce2(ws, bsrc, dw, db, S, Sb_ext, K, Cout, first ? 4 : Cin, ksize * ksize, first, beta,
-                                 scale, dscale, rs);
-  return launch_reduce2(ws, wsb_used, dw, db, S, Sb, K, Cout, first ? 4 : Cin, ksize * ksize, first, beta, scale, dscale,
-                        rs);
+  if (p.bias == WB_EXT_FOLD)
+    hipLaunchKernelGGL(bias_rows_reduce_kernel, dim3(p.Sb_ext), dim3(256), 0, s, bext, wsb, bext_rows, Cout, p.bias_rpb);
+  const bool ext = p.bias == WB_EXT || p.bias == WB_EXT_FOLD;
+  const float* bsrc = p.bias == WB_NONE ? nullptr : p.bias == WB_EXT ? bext : wsb;
+  return launch_reduce2(ws, bsrc, dw, db, S, ext ? p.Sb_ext : p.Sb, K, Cout, first ? 4 : Cin, ksize * ksize, first, beta,
+                        scale, dscale, s);
 }
 
-// dt: element type of dy / x (DT_BF16 = 0, DT_F16 = 1); the gradients are fp32.  The result is
-// multiplied by scale and, when dscale is not null, by the device scalar dscale[0] (1 / loss scale).
-// bext (optional): [bext_rows][Cout] fp32 bias partials of dy already summed by its producer (the data-gradient
-// epilogue): db comes from them, the kernels here do no bias work
 extern "C" int can_bias_rows_reduce(const float* in, float* out, int R, int C, int rows_out, void* stream) {
   if (C % 64 || C > 1024 || R < 1 || rows_out < 1) return -2;
   const int rpb = (R + rows_out - 1) / rows_out;
@@ -1419,12 +1246,25 @@ extern "C" int can_bias_rows_reduce(const float* in, float* out, int R, int C, i
   return g;                                   // rows written
 }
 
-extern "C" int can_conv_wgrad(const void* dy, const void* x, float* ws, float* wsb, float* dw, float* db, int N,
-                              int H, int W, int Cin, int Cout, int ksize, int dil, int first, int S, int mslice,
-                              int cfg, float beta, float scale, const float* dscale, int dt, void* stream,
-                              const float* bext, int bext_rows) {
-  CAN_DT_DISPATCH(dt, conv_wgrad_impl<DT>(dy, x, ws, wsb, dw, db, N, H, W, Cin, Cout, ksize, dil, first, S, mslice,
-                                          cfg, beta, scale, dscale, stream, bext, bext_rows));
+// Plans the launch (plan_wgrad under the process's dispatch config) and executes it.
+// dt: element type of dy / x (DT_BF16 = 0, DT_F16 = 1); the gradients are fp32.  The result is
+// multiplied by scale and, when dscale is not null, by the device scalar dscale[0] (1 / loss scale).
+// bext (optional): [bext_rows][Cout] fp32 bias partials of dy already summed by its producer (the data-gradient
+// epilogue): db comes from them, the kernels here do no bias work.
+// ws: ws_floats floats of scratch for the plan's slabs and bias area; -21: fewer than the plan needs (returned, like
+// the plan's own errors, before anything is launched)
+extern "C" int can_conv_wgrad(const void* dy, const void* x, float* ws, long long ws_floats, float* dw, float* db,
+                              int N, int H, int W, int Cin, int Cout, int ksize, int dil, int first, float beta,
+                              float scale, const float* dscale, int dt, void* stream, const float* bext,
+                              int bext_rows) {
+  WgradQuery q = wgrad_query(N, H, W, Cin, Cout, ksize, dil, first);
+  q.want_db = db != nullptr;
+  q.bext_rows = bext ? bext_rows : 0;
+  const WgradPlan p = plan_wgrad(q, g_dispatch, can_device_cus());
+  if (p.err) return p.err;
+  if (p.ws_floats > ws_floats) return -21;
+  CAN_DT_DISPATCH(dt, conv_wgrad_impl<DT>(dy, x, ws, dw, db, N, H, W, Cin, Cout, ksize, dil, beta, scale, dscale,
+                                          (hipStream_t)stream, bext, bext_rows, p));
 }
 
 // Batched 1x1 weight gradient without bias: nb problems dW_b[Cout][Cin] = sum_m dY_b[m][co] X_b[m][ci]
@@ -1434,8 +1274,6 @@ template <int DT>
 static int conv_wgrad_1x1_batched_impl(const void* dy, const void* x, float* ws, float* dw, int M, int W, int Cin,
                                        int Cout, int nb, long long dy_bs, long long x_bs, long long dw_bs, int S,
                                        int mslice, float beta, float scale, const float* dscale, hipStream_t s) {
-  using namespace can;
-  if (Cout % 256 || Cin % 256 || W % 64 || mslice % 64 || M % 64 || (long long)M * Cout * 2 >= 0x7fffffffLL) return -3;
   WgradArgs2 a;
   a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.zero = (const bf16_t*)can_zero_page(); a.ws = ws; a.wsb = nullptr;
   if (!a.zero) return -7;
@@ -1444,7 +1282,8 @@ static int conv_wgrad_1x1_batched_impl(const void* dy, const void* x, float* ws,
   a.fdW = make_fastdiv((uint32_t)W); a.fdH = make_fastdiv((uint32_t)(M / W)); a.fdC = make_fastdiv((uint32_t)Cin);
   a.Mreal = M; a.tx64 = W / 64; a.fdTX = make_fastdiv((uint32_t)a.tx64);
   a.nb = nb; a.dy_bs = dy_bs; a.x_bs = x_bs;
-  int rc = launch_wgrad3<DT, 4, 2, 2>(a, s);
+  constexpr WgradTile t = *find_wgrad_tile(9);
+  int rc = launch_wgrad3<DT, t.cfg>(a, (Cout / t.TCo) * (Cin / t.TK) * S * nb, s);
   if (rc) return rc;
   const size_t slabs = (size_t)S * Cin * Cout;
   for (int b = 0; b < nb; ++b) {
@@ -1455,12 +1294,16 @@ static int conv_wgrad_1x1_batched_impl(const void* dy, const void* x, float* ws,
   return 0;
 }
 
-extern "C" int can_conv_wgrad_1x1_batched(const void* dy, const void* x, float* ws, float* dw, int M, int W, int Cin,
-                                          int Cout, int nb, long long dy_bs, long long x_bs, long long dw_bs, int S,
-                                          int mslice, float beta, float scale, const float* dscale, int dt,
-                                          void* stream) {
-  CAN_DT_DISPATCH(dt, conv_wgrad_1x1_batched_impl<DT>(dy, x, ws, dw, M, W, Cin, Cout, nb, dy_bs, x_bs, dw_bs, S,
-                                                      mslice, beta, scale, dscale, (hipStream_t)stream));
+// ncu: the CUs the launch is planned for (dispatch ctx_wgrad_cus); ws_floats as can_conv_wgrad (-21)
+extern "C" int can_conv_wgrad_1x1_batched(const void* dy, const void* x, float* ws, long long ws_floats, float* dw,
+                                          int M, int W, int Cin, int Cout, int nb, long long dy_bs, long long x_bs,
+                                          long long dw_bs, int ncu, float beta, float scale, const float* dscale,
+                                          int dt, void* stream) {
+  const WgradBatchedPlan p = plan_wgrad_1x1_batched(M, W, Cin, Cout, nb, ncu);
+  if (p.err || W < 1) return -3;
+  if (p.ws_floats > ws_floats) return -21;
+  CAN_DT_DISPATCH(dt, conv_wgrad_1x1_batched_impl<DT>(dy, x, ws, dw, M, W, Cin, Cout, nb, dy_bs, x_bs, dw_bs, p.S,
+                                                      p.mslice, beta, scale, dscale, (hipStream_t)stream));
 }
 
 // first-layer slab reduction: ws [S][36][64] (k = tap*4 + c), wsb [S][64] -> dW [64][3][3][3], db [64]

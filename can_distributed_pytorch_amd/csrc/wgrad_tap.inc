@@ -321,14 +321,4 @@ static int launch_wgrad_tap(const TapArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(kfn, dim3(ntile * a.S), dim3(G::NW * 64), G::LDS, s, a);
   return (int)hipGetLastError();
 }
-
-// the output-channel tile of the tap-ring kernel for a layer: 128 (Cout % 128 == 0), 64 (Cout == 64), else 0
-static int wgrad_tap_tco(int Cout) { return (Cout % 128 == 0) ? 128 : (Cout == 64) ? 64 : 0; }
-
-// the tap-ring kernel applies: 3x3, dilation 1 / 2, Cin % 64 == 0, Cout % 128 == 0 or Cout == 64, W % 8 == 0,
-// operands addressable by 32-bit buffer offsets
-static bool wgrad_tap_ok(int N, int H, int W, int Cin, int Cout, int ksize, int dil) {
-  const long long M = (long long)N * H * W;
-  return ksize == 3 && (dil == 1 || dil == 2) && Cin % 64 == 0 && wgrad_tap_tco(Cout) != 0 && W % 8 == 0 && W >= 8 &&
-         H >= 1 && M * Cout * 2 < 0x7fffff00LL && M * Cin * 2 < 0x7fffff00LL;
-}
+// (the shapes the kernel takes: wgrad_tap_ok / wgrad_tap_tco in wgrad_plan.h)

@@ -339,19 +339,25 @@ class WgradWorkspace:
     """One fp32 scratch buffer for the split-pixel partial slabs, grown on demand
     (allocated outside any captured region, never inside a launch function)."""
 
-    def __init__(self, device, target_blocks: int = 1024):
+    def __init__(self, device):
         self.device = torch.device(device)
-        self.target_blocks = target_blocks
         self.buf = torch.empty(0, dtype=torch.float32, device=self.device)
+        self._plans = {}          # answers of plan(): the eager step asks once per weight gradient
 
     def plan(self, m: int, ci: int, co: int, ksize: int, first: bool, dil: int = 1, w: int = 0):
-        """(slices, pixels per slice, kernel config, workspace floats) of one weight gradient; w (the map width, 0 =
-        unknown) lets the planner pick the width-dependent tap-ring kernel."""
-        C = _ext.require()
-        s, mslice, cfg = C.wgrad_plan(m, ci, co, ksize, int(first), self.target_blocks, dil, w)
-        ktot = 64 if first else ksize * ksize * ci
-        need = s * ktot * co + max(s, 512) * co      # slabs + bias partials (v2 path: 512 column-sum parts)
-        return s, mslice, cfg, need
+        """(slices, pixels per slice, kernel config, workspace floats) of one weight gradient, from the launch plan
+        (csrc/wgrad_plan.h); w (the map width, 0 = unknown) lets the planner pick the width-dependent tap-ring
+        kernel.  The image height is not known here: the launcher's refusal of maps under 2 x 2 is its own."""
+        key = (m, ci, co, ksize, first, dil, w, dispatch.current())
+        got = self._plans.get(key)
+        if got is None:
+            if w <= 0 or m % w:
+                w = 0
+            p = _ext.require().wgrad_launch_plan(1, 0, w, m, 4 if first else ci, co, ksize, dil, int(first))
+            if p["err"]:
+                raise ValueError(f"weight gradient {ci} -> {co} ({ksize}x{ksize}, {m} pixels): plan error {p['err']}")
+            got = self._plans[key] = (p["S"], p["mslice"], p["cfg"], p["ws_floats"])
+        return got
 
     def reserve(self, need: int) -> torch.Tensor:
         if self.buf.numel() < need:
@@ -399,18 +405,15 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional
                        first=first, ws=ws, beta=beta if c == 0 else 1.0, scale=scale, dscale=dscale,
                        bias_partials=bias_partials if c == 0 else None)
         return
-    s, mslice, cfg, need = ws.plan(n * h * w, ci, co, ksize, first, dil, w)
-    buf = ws.reserve(need)
-    ktot = 64 if first else ksize * ksize * ci
-    wsb_ptr = buf.data_ptr() + 4 * s * ktot * co
+    buf = ws.reserve(ws.plan(n * h * w, ci, co, ksize, first, dil, w)[3])
     bx, brows = 0, 0
     if bias_partials is not None and db is not None:
         if bias_partials.dtype != torch.float32 or not bias_partials.is_contiguous() or bias_partials.dim() != 2 or \
                 bias_partials.shape[1] != co or co > 1024:
             raise ValueError(f"bias_partials must be a contiguous fp32 [rows, {co}] tensor (Cout <= 1024)")
         bx, brows = bias_partials.data_ptr(), bias_partials.shape[0]
-    C.conv_wgrad(dy.data_ptr(), x.data_ptr(), buf.data_ptr(), wsb_ptr, dw.data_ptr(),
-                 db.data_ptr() if db is not None else 0, n, h, w, ci, co, ksize, dil, int(first), s, mslice, cfg,
+    C.conv_wgrad(dy.data_ptr(), x.data_ptr(), buf.data_ptr(), buf.numel(), dw.data_ptr(),
+                 db.data_ptr() if db is not None else 0, n, h, w, ci, co, ksize, dil, int(first),
                  float(beta), float(scale), dscale.data_ptr() if dscale is not None else 0, dt_code(dy.dtype),
                  _ext.stream_ptr(x.device), bx, brows)
 
@@ -427,26 +430,23 @@ def _ctx_wgrad_cus() -> int:
 def wgrad_1x1_batched_plan(m: int, nb: int, ci: int, co: int, ncu: int = 0):
     """(S, mslice, workspace floats) of the batched 1x1 weight gradient: one round of 256x256 tiles over ncu CUs
     (0: ``_ctx_wgrad_cus()``)."""
-    ncu = ncu or _ctx_wgrad_cus()
-    ntile = (co // 256) * (ci // 256) * nb
-    s = max(1, ncu // ntile)
-    mslice = -(-m // s)
-    mslice = -(-mslice // 64) * 64
-    s = -(-m // mslice)
-    return s, mslice, nb * s * ci * co
+    p = _ext.require().wgrad_1x1_batched_launch_plan(m, 0, ci, co, nb, ncu or _ctx_wgrad_cus())
+    if not p["S"]:
+        raise ValueError(f"batched 1x1 weight gradient: no plan for {nb} x {ci} -> {co} over {m} pixels")
+    return p["S"], p["mslice"], p["ws_floats"]      # a sizing answer also for maps the launch refuses (p["err"])
 
 
 def wgrad_1x1_batched_ok(dy: torch.Tensor, x: torch.Tensor, dws) -> bool:
-    """Shapes / layouts the batched kernel takes: [nb,N,H,W,C] operands with W % 64 == 0, channels % 256 == 0,
-    and the nb fp32 [Co,Ci,1,1] outputs laid out back to back (consecutive slots of the gradient arena)."""
+    """Shapes / layouts the batched kernel takes: [nb,N,H,W,C] operands of a shape its launch plan accepts (W % 64 ==
+    0, channels % 256 == 0, 32-bit operand addressing: the per-item launches chunk instead) and the nb fp32
+    [Co,Ci,1,1] outputs laid out back to back (consecutive slots of the gradient arena)."""
     if dy.dim() != 5 or x.dim() != 5 or not (dy.is_contiguous() and x.is_contiguous()):
         return False
     nb, n, h, w, co = dy.shape
     ci = x.shape[-1]
-    if tuple(x.shape[:4]) != (nb, n, h, w) or w % 64 or co % 256 or ci % 256 or (n * h * w) % 64:
+    if tuple(x.shape[:4]) != (nb, n, h, w) or w < 1 or \
+            _ext.require().wgrad_1x1_batched_launch_plan(n * h * w, w, ci, co, nb, _ctx_wgrad_cus())["err"]:
         return False
-    if n * h * w * max(ci, co) * 2 >= 2 ** 31:
-        return False                       # 32-bit operand addressing: the per-item launches chunk instead
     if len(dws) != nb or any(d.dtype != torch.float32 or not d.is_contiguous() or tuple(d.shape) != (co, ci, 1, 1)
                              for d in dws):
         return False
@@ -466,10 +466,9 @@ def conv_wgrad_1x1_batched(dy: torch.Tensor, x: torch.Tensor, dws, *, ws: "Wgrad
     nb, n, h, w, co = dy.shape
     ci = x.shape[-1]
     m = n * h * w
-    s, mslice, need = wgrad_1x1_batched_plan(m, nb, ci, co)
-    buf = ws.reserve(need)
-    C.conv_wgrad_1x1_batched(dy.data_ptr(), x.data_ptr(), buf.data_ptr(), dws[0].data_ptr(), m, w, ci, co, nb,
-                             m * co, m * ci, co * ci, s, mslice, float(beta), float(scale),
+    buf = ws.reserve(wgrad_1x1_batched_plan(m, nb, ci, co)[2])
+    C.conv_wgrad_1x1_batched(dy.data_ptr(), x.data_ptr(), buf.data_ptr(), buf.numel(), dws[0].data_ptr(), m, w, ci,
+                             co, nb, m * co, m * ci, co * ci, _ctx_wgrad_cus(), float(beta), float(scale),
                              dscale.data_ptr() if dscale is not None else 0, dt_code(dy.dtype),
                              _ext.stream_ptr(x.device))
 

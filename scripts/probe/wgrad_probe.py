@@ -22,8 +22,8 @@ def main():
         lib = ctypes.CDLL(os.path.join(ROOT, "scripts", "probe", "bin", f"wgrad_probe{m}.so"))
         f = lib.can_conv_wgrad
         f.restype = ctypes.c_int
-        f.argtypes = ([ctypes.c_void_p] * 6 + [ctypes.c_int] * 11 + [ctypes.c_float] * 2 + [ctypes.c_void_p] +
-                      [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int])
+        f.argtypes = ([ctypes.c_void_p] * 3 + [ctypes.c_longlong] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 8 +
+                      [ctypes.c_float] * 2 + [ctypes.c_void_p] + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int])
         fns[m] = f
     n = 8
     ws = C.WgradWorkspace("cuda")
@@ -33,16 +33,15 @@ def main():
         dy = torch.randn(n, h, w, co, device="cuda").to(torch.bfloat16)
         dw = torch.empty(co, ci, 3, 3, device="cuda")
         db = torch.empty(co, device="cuda")
-        s, mslice, cfg, need = ws.plan(n * h * w, ci, co, 3, False, dil)
+        s, _, cfg, need = ws.plan(n * h * w, ci, co, 3, False, dil, w)      # the launcher plans the same way itself
         buf = ws.reserve(need)
-        wsb = buf.data_ptr() + 4 * s * 9 * ci * co
         fl = 2.0 * n * h * w * ci * co * 9
         res = {m: [] for m in fns}
         for rnd in range(3):
             for m, f in fns.items():
                 def call():
-                    rc = f(dy.data_ptr(), x.data_ptr(), buf.data_ptr(), wsb, dw.data_ptr(), db.data_ptr(), n, h, w, ci,
-                           co, 3, dil, 0, s, mslice, cfg, 0.0, 1.0, None, 0, st, None, 0)
+                    rc = f(dy.data_ptr(), x.data_ptr(), buf.data_ptr(), buf.numel(), dw.data_ptr(), db.data_ptr(), n, h, w,
+                           ci, co, 3, dil, 0, 0.0, 1.0, None, 0, st, None, 0)
                     assert rc == 0, rc
                 for _ in range(3):
                     call()

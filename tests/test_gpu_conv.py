@@ -122,6 +122,8 @@ def test_conv_wgrad_v2_row_aligned(n, h, w, ci, co, dil, bias, dispatch_cfg):
     from can_distributed_pytorch_amd.ops import conv as C
     dispatch_cfg(wgrad_tap=0)
     assert _ext.require().wgrad_plan(n * h * w, ci, co, 3, 0, 1024, dil, w)[2] == 9
+    plan = _ext.require().wgrad_launch_plan(n, h, w, n * h * w, ci, co, 3, dil, want_db=bias)
+    assert (plan["cfg"], plan["family"], plan["ragged"]) == (9, 2, w % 64 != 0), plan     # family 2: the v2 kernel
     torch.manual_seed(6)
     x = torch.randn(n, h, w, ci, device="cuda").to(torch.bfloat16)
     dy = torch.randn(n, h, w, co, device="cuda").to(torch.bfloat16)
@@ -258,6 +260,63 @@ def test_conv_wgrad_1x1_batched(dtype):
         _close(dws[b].view(c, c), ref)
 
 
+_SENTINEL = 7.0
+
+
+@pytest.mark.parametrize("rows,cols,cfg", [(6, 8, 1), (6, 64, 12)])
+def test_conv_wgrad_refuses_a_short_workspace(rows, cols, cfg, dispatch_cfg):
+    """The launcher plans its own launch and is told the workspace's size: one float short of the plan's need it
+    returns -21 before anything is launched (dw, db and the workspace keep their sentinel); with the whole need it
+    runs, and gives the front end's result bit for bit.  cfg 1: LDS-DMA GEMM; cfg 12: tap ring."""
+    from can_distributed_pytorch_amd.ops import _ext
+    from can_distributed_pytorch_amd.ops import conv as C
+    ext = _ext.require()
+    dispatch_cfg(wgrad_tap=3 if cfg == 12 else 0)
+    ci, co = 64, 128
+    _, _, got, need = C.WgradWorkspace("cuda").plan(rows * cols, ci, co, 3, False, 1, cols)
+    assert got == cfg
+    torch.manual_seed(9)
+    x = torch.randn(1, rows, cols, ci, device="cuda").to(torch.bfloat16)
+    dy = torch.randn(1, rows, cols, co, device="cuda").to(torch.bfloat16)
+    buf = torch.full((need,), _SENTINEL, device="cuda")
+    dw, db = torch.full((co, ci, 3, 3), _SENTINEL, device="cuda"), torch.full((co,), _SENTINEL, device="cuda")
+
+    def launch(ws_floats):
+        ext.conv_wgrad(dy.data_ptr(), x.data_ptr(), buf.data_ptr(), ws_floats, dw.data_ptr(), db.data_ptr(), 1, rows,
+                       cols, ci, co, 3, 1, 0, 0.0, 1.0, 0, C.dt_code(dy.dtype), _ext.stream_ptr(x.device))
+
+    with pytest.raises(RuntimeError, match="rc=-21"):
+        launch(need - 1)
+    torch.cuda.synchronize()
+    assert bool((dw == _SENTINEL).all()) and bool((db == _SENTINEL).all()) and bool((buf == _SENTINEL).all())
+    launch(need)
+    dw2, db2 = torch.empty_like(dw), torch.empty_like(db)
+    C.conv_wgrad(dy, x, dw2, db2, ksize=3)
+    torch.cuda.synchronize()
+    assert torch.equal(dw, dw2) and torch.equal(db, db2)
+
+
+def test_conv_wgrad_1x1_batched_refuses_a_short_workspace():
+    from can_distributed_pytorch_amd.ops import _ext
+    from can_distributed_pytorch_amd.ops import conv as C
+    ext = _ext.require()
+    nb, h, w, c = 4, 2, 64, 256
+    m = h * w
+    ncu = C._ctx_wgrad_cus()
+    need = C.wgrad_1x1_batched_plan(m, nb, c, c)[2]
+    torch.manual_seed(10)
+    x = torch.randn(nb, 1, h, w, c, device="cuda").to(torch.bfloat16)
+    dy = torch.randn(nb, 1, h, w, c, device="cuda").to(torch.bfloat16)
+    buf = torch.full((need,), _SENTINEL, device="cuda")
+    arena = torch.full((nb * c * c,), _SENTINEL, device="cuda")
+    with pytest.raises(RuntimeError, match="rc=-21"):
+        ext.conv_wgrad_1x1_batched(dy.data_ptr(), x.data_ptr(), buf.data_ptr(), need - 1, arena.data_ptr(), m, w, c, c,
+                                   nb, m * c, m * c, c * c, ncu, 0.0, 1.0, 0, C.dt_code(dy.dtype),
+                                   _ext.stream_ptr(x.device))
+    torch.cuda.synchronize()
+    assert bool((arena == _SENTINEL).all()) and bool((buf == _SENTINEL).all())
+
+
 @pytest.mark.parametrize("n,h,w,ci,co,dil,cfg,bias", [
     (1, 6, 64, 128, 256, 1, 10, True), (2, 5, 128, 128, 512, 2, 10, False), (1, 9, 64, 256, 128, 2, 11, True),
     (2, 4, 64, 512, 128, 1, 11, True),
@@ -270,6 +329,8 @@ def test_conv_wgrad_v2_half_tiles(n, h, w, ci, co, dil, cfg, bias, dispatch_cfg)
     from can_distributed_pytorch_amd.ops import conv as C
     dispatch_cfg(wgrad_tap=0)
     assert _ext.require().wgrad_plan(n * h * w, ci, co, 3, 0, 1024, dil, w)[2] == cfg
+    plan = _ext.require().wgrad_launch_plan(n, h, w, n * h * w, ci, co, 3, dil, want_db=bias)
+    assert (plan["cfg"], plan["family"], plan["ragged"]) == (cfg, 2, w % 64 != 0), plan   # family 2: the v2 kernel
     torch.manual_seed(8)
     x = torch.randn(n, h, w, ci, device="cuda").to(torch.bfloat16)
     dy = torch.randn(n, h, w, co, device="cuda").to(torch.bfloat16)

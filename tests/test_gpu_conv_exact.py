@@ -365,6 +365,10 @@ def test_bias_partials(n, h, w, ci, co, dil, epi, splitk, many, dtype, dispatch_
 
 
 # ---------------------------------------------------------------------------------------------------- weight gradient
+_RED_KIND = {"tiled": 0, "r1": 1, "r4": 4, "r16": 16, "r64": 64}     # the launch plan's "reduce" (wgrad_plan.h)
+_WG_GLDS, _WG_GLDS2 = 1, 2                                            # ... and "family": the v1 / v2 LDS-DMA kernels
+
+
 def _reduce_kernel(S, K, co, ci, taps, first):
     """The slab reduction conv_wgrad.hip launch_reduce2 picks: the LDS-transposing tiled kernel, or
     wgrad_reduce2_kernel<1 / 4 / 64 / 16>."""
@@ -404,8 +408,19 @@ def _check_wgrad(n, h, w, ci, co, k, dil, dtype, cfg, red=None, beta=0.0, scale=
     ws = C.WgradWorkspace(DEV)
     s, _, got_cfg, _ = ws.plan(M, ci, co, k, first, dil, w)
     assert got_cfg == cfg, (got_cfg, s)
+    plan = ext.wgrad_launch_plan(n, h, w, M, ci, co, k, dil, int(first), want_db=bias)
+    if plan["err"]:
+        assert plan["err"] == -3 and (h < 2 or w < 2), plan    # the launch below is refused with this code
+    else:
+        assert (plan["cfg"], plan["S"]) == (cfg, s), plan
     if red is not None:
         assert _reduce_kernel(s, 64 if first else k * k * ci, co, 4 if first else ci, k * k, first) == red, s
+        assert plan["reduce"] == _RED_KIND[red], plan
+    if cfg in (9, 10, 11) and not plan["err"]:
+        # the kernel that runs: the pipelined v2 kernel on the 3x3 layers (row-aligned and ragged widths alike), the v1
+        # kernel of the same tiles on a 1x1 layer whose width is no multiple of 64
+        assert plan["family"] == (_WG_GLDS if k == 1 and w % 64 else _WG_GLDS2), plan
+        assert plan["ragged"] == (k == 3 and w % 64 != 0), plan
     dw, db = dw0.clone(), (db0.clone() if bias else None)
     dsc = None if dscale_k is None else torch.tensor([ds], dtype=torch.float32, device=DEV)
     launch(lambda: C.conv_wgrad(dy16, x16, dw, db, ksize=k, dil=dil, first=first, ws=ws, beta=beta, scale=scale,
