@@ -66,23 +66,17 @@ int can_grad_nonfinite(const float* g, size_t n, float* flags, void* stream);
 int can_split_x3(const float* src, void* dst, long long M, int C, int stride, int mode, int pattern, void* stream);
 int can_scale_update(const float* flags, float* scaler, int interval, float growth, float backoff, float max_scale,
                      void* stream);
-int can_pack_conv(const float* w, void* fwd, void* dgr, int Co, int Ci, int taps, int first, int dt, void* stream);
 int can_pack_multi(const long long* desc, int layers, int max_tiles, int dt, void* stream);
-int can_sgd_pack(const long long* desc, int rows, int max_tiles, long long goff, long long boff, float lr,
-                 float momentum, float gscale, float* flags, const float* lr_dev, int dt, void* stream);
 int can_adam(float* p, float* m, float* v, const float* g, size_t n, float lr, double beta1, double beta2, float eps,
              float wd, int decoupled, float gscale, int step, int* t_dev, float* flags, const float* lr_dev,
              void* stream, const float* gmul);
+// the fused optimizer step; eoff != 0: the EMA of the parameters is updated in the same launch (eoff: the EMA arena's
+// offset from the masters in floats, ema_t: device count of applied updates)
 int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
                  long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
                  int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt, void* stream,
-                 const float* gmul);
-// EMA of the parameters: fused into the optimizer launch (eoff: the EMA arena's offset from the masters in floats,
-// ema_t: device count of applied updates), the stand-alone update, and the master <-> EMA swap launch
-int can_opt_pack_ema(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
-                     long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
-                     int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt, void* stream,
-                     const float* gmul, long long eoff, double ema_decay, int ema_warmup, int* ema_t);
+                 const float* gmul, long long eoff, double ema_decay, int ema_warmup, int* ema_t);
+// the stand-alone EMA update and the master <-> EMA swap launch
 int can_ema(float* e, const float* p, size_t n, double decay, int warmup, int step, int* t_dev, float* flags,
             void* stream);
 int can_swap_pack(const long long* desc, int rows, int max_tiles, long long eoff, int dt, void* stream);

@@ -13,7 +13,6 @@
 //   sgd_momentum        torch.optim.SGD(momentum=0.95) step over the flat fp32
 //                       arena, gradient averaging folded in, skipped on a
 //                       device-side non-finite flag             train.py:126
-//   pack_conv           fp32 [Co][Ci][kh][kw] -> bf16 forward / dgrad packs
 //   img_to_nhwc4        [N,3,H,W] fp32 -> [N,H,W,4] bf16 (first-layer input)
 #include "common.h"
 
@@ -261,34 +260,50 @@ __global__ void __launch_bounds__(1024) head_reduce_kernel(const float* __restri
 // lr_dev (optional): the learning rate read from device memory, so a captured
 // step follows an lr schedule (the host updates the scalar between replays).
 // Vectorised float4 over a 16-B aligned arena.
+//
+// The prologue of every kernel that steps under the flags (sgd_momentum, pack_multi, adam, ema): true = skip.  latch:
+// this is the one thread of the launch that writes flags[3].
+__device__ __forceinline__ bool opt_skip(float* flags, bool latch) {
+  if (flags == nullptr) return false;
+  if (flags[0] != 0.f) {
+    if (latch) flags[3] = 1.f;
+    return true;
+  }
+  return flags[2] != 0.f;
+}
+// One element of the step past the first, for the stand-alone and the fused kernel alike (as adam1 below is for Adam).
+// WD: torch.optim.SGD's coupled weight decay, g += wd * p ahead of the momentum.  Explicit multiply / fma in this
+// order: the same rounding steps in every caller whatever the compiler would contract.
+template <bool WD>
+__device__ __forceinline__ void sgd1(float& p, float& b, float g, float lr, float momentum, float gscale, float wd) {
+  g = __fmul_rn(g, gscale);
+  if constexpr (WD) g = fmaf(wd, p, g);
+  b = fmaf(momentum, b, g);
+  p = fmaf(-lr, b, p);
+}
 __global__ void __launch_bounds__(256) sgd_momentum_kernel(float4* __restrict__ p, float4* __restrict__ buf,
                                                            const float4* __restrict__ g, size_t n4, float lr,
                                                            float momentum, float gscale, int first,
                                                            float* __restrict__ flags, const float* __restrict__ lr_dev,
                                                            const float* __restrict__ gmul) {
-  if (flags != nullptr) {
-    const bool bad_loss = flags[0] != 0.f;
-    if (bad_loss && blockIdx.x == 0 && threadIdx.x == 0) flags[3] = 1.f;
-    if (bad_loss || flags[2] != 0.f) return;
-  }
+  if (opt_skip(flags, blockIdx.x == 0 && threadIdx.x == 0)) return;
   if (lr_dev != nullptr) lr = lr_dev[0];
   // gmul (optional): a device-side gradient multiplier (the clip coefficient of grad_norm_final_kernel), folded into
   // gscale by ONE fp32 product per thread, so the step equals passing float(gscale) * float(gmul[0]) from the host
   if (gmul != nullptr) gscale = __fmul_rn(gscale, gmul[0]);
   for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    float4 gv = g[i];
-    gv.x = __fmul_rn(gv.x, gscale); gv.y = __fmul_rn(gv.y, gscale);
-    gv.z = __fmul_rn(gv.z, gscale); gv.w = __fmul_rn(gv.w, gscale);
-    float4 b;
-    if (first) b = gv;
-    else {
+    const float4 gv = g[i];
+    float4 pv = p[i], b;
+    if (first) {
+      b = make_float4(__fmul_rn(gv.x, gscale), __fmul_rn(gv.y, gscale), __fmul_rn(gv.z, gscale),
+                      __fmul_rn(gv.w, gscale));
+      pv.x = fmaf(-lr, b.x, pv.x); pv.y = fmaf(-lr, b.y, pv.y); pv.z = fmaf(-lr, b.z, pv.z); pv.w = fmaf(-lr, b.w, pv.w);
+    } else {
       b = buf[i];
-      b.x = fmaf(momentum, b.x, gv.x); b.y = fmaf(momentum, b.y, gv.y);
-      b.z = fmaf(momentum, b.z, gv.z); b.w = fmaf(momentum, b.w, gv.w);
+      sgd1<false>(pv.x, b.x, gv.x, lr, momentum, gscale, 0.f); sgd1<false>(pv.y, b.y, gv.y, lr, momentum, gscale, 0.f);
+      sgd1<false>(pv.z, b.z, gv.z, lr, momentum, gscale, 0.f); sgd1<false>(pv.w, b.w, gv.w, lr, momentum, gscale, 0.f);
     }
     buf[i] = b;
-    float4 pv = p[i];
-    pv.x = fmaf(-lr, b.x, pv.x); pv.y = fmaf(-lr, b.y, pv.y); pv.z = fmaf(-lr, b.z, pv.z); pv.w = fmaf(-lr, b.w, pv.w);
     p[i] = pv;
   }
 }
@@ -389,28 +404,6 @@ __global__ void scale_update_kernel(const float* __restrict__ flag, float* __res
 }
 
 // ---------------------------------------------------------------- packing
-// w fp32 [Co][Ci][k][k] -> fwd bf16 [Co][tap][Ci] and dgrad bf16 [Ci][8-tap][Co]
-// (first layer: fwd [Co][64] with k = tap*4 + c, no dgrad).
-template <int DT>
-__global__ void __launch_bounds__(256) pack_conv_kernel(const float* __restrict__ w, bf16_t* __restrict__ fwd,
-                                                        bf16_t* __restrict__ dgr, int Co, int Ci, int taps,
-                                                        int first) {
-  const size_t total = (size_t)Co * Ci * taps;
-  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int tap = i % taps;
-    const size_t r = i / taps;
-    const int ci = r % Ci;
-    const int co = r / Ci;
-    const unsigned short v = f2h<DT>(w[i]);
-    if (first) {
-      fwd[(size_t)co * 64 + tap * 4 + ci] = v;
-    } else {
-      fwd[((size_t)co * taps + tap) * Ci + ci] = v;
-      if (dgr) dgr[((size_t)ci * taps + (taps - 1 - tap)) * Co + co] = v;
-    }
-  }
-}
-
 // All layers' packs in one launch: blockIdx.y = descriptor row, rows of kPackRow int64
 //   {w, fwd, dgr, Co, Ci, taps, first, mode, fwd2, dgr2, si, n}
 // mode 0: a conv weight [Co][Ci][taps] -> fwd [Co][tap][Ci] and dgr [Ci][taps-1-tap][Co] (first: fwd [Co][64],
@@ -534,11 +527,7 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
   const int mode = (int)d[7];
   float lr = sa.lr;
   if constexpr (OPT != OPT_NONE && OPT != OPT_SWAP) {
-    if (sa.flags != nullptr) {
-      const bool bad_loss = sa.flags[0] != 0.f;
-      if (bad_loss && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) sa.flags[3] = 1.f;
-      if (bad_loss || sa.flags[2] != 0.f) return;
-    }
+    if (opt_skip(sa.flags, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)) return;
     if (sa.lr_dev != nullptr) lr = sa.lr_dev[0];
     if constexpr (OPT != OPT_ADAM) {              // (Adam: adam_coef folds gmul in)
       if (sa.gmul != nullptr) sa.gscale = __fmul_rn(sa.gscale, sa.gmul[0]);
@@ -546,8 +535,10 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
   }
   AdamCoef ac{};                // Adam: filled in below, past the exits of the blocks that have no work
   float ew = 0.f;               // EMA: likewise
-  // one element of the SGD step (sgd_momentum_kernel's order of operations)
-  // (explicit multiply / fma: the same rounding steps in both kernels whatever the compiler would contract)
+  auto sgd = [&](float& p, float& b, float g) {
+    sgd1<OPT == OPT_SGD_WD>(p, b, g, lr, sa.momentum, sa.gscale, sa.wd);
+  };
+  // one element of the optimizer step (sgd1 / adam1: the stand-alone kernels' operations, in their order)
   auto step1 = [&](float* pw, float pv, float gv, float bv) -> float {
     float ev = 0.f;
     if constexpr (EMA) ev = pw[sa.eoff];
@@ -556,19 +547,13 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
       adam1(ac, pv, bv, vv, gv);
       pw[sa.boff] = bv;
       pw[sa.voff] = vv;
-      pw[0] = pv;
-      if constexpr (EMA) pw[sa.eoff] = ema1(ew, as_stored<OPT>(pv), ev);
-      return pv;
     } else {
-      gv = __fmul_rn(gv, sa.gscale);
-      if constexpr (OPT == OPT_SGD_WD) gv = fmaf(sa.wd, pv, gv);
-      const float b = fmaf(sa.momentum, bv, gv);
-      pw[sa.boff] = b;
-      const float np = fmaf(-lr, b, pv);
-      pw[0] = np;
-      if constexpr (EMA) pw[sa.eoff] = ema1(ew, as_stored<OPT>(np), ev);
-      return np;
+      sgd(pv, bv, gv);
+      pw[sa.boff] = bv;
     }
+    pw[0] = pv;
+    if constexpr (EMA) pw[sa.eoff] = ema1(ew, as_stored<OPT>(pv), ev);
+    return pv;
   };
   // one element of the swap: the EMA copy lands in the master slot (and is what the packs are made from)
   auto swap1 = [&](float* pw) -> float {
@@ -669,16 +654,8 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const long long* __rest
         float4 b = *reinterpret_cast<const float4*>(pw + sa.boff);
         float4 e{};
         if constexpr (EMA) e = *reinterpret_cast<const float4*>(pw + sa.eoff);
-        gv.x = __fmul_rn(gv.x, sa.gscale); gv.y = __fmul_rn(gv.y, sa.gscale);
-        gv.z = __fmul_rn(gv.z, sa.gscale); gv.w = __fmul_rn(gv.w, sa.gscale);
-        if constexpr (OPT == OPT_SGD_WD) {
-          gv.x = fmaf(sa.wd, v.x, gv.x); gv.y = fmaf(sa.wd, v.y, gv.y);
-          gv.z = fmaf(sa.wd, v.z, gv.z); gv.w = fmaf(sa.wd, v.w, gv.w);
-        }
-        b.x = fmaf(sa.momentum, b.x, gv.x); b.y = fmaf(sa.momentum, b.y, gv.y);
-        b.z = fmaf(sa.momentum, b.z, gv.z); b.w = fmaf(sa.momentum, b.w, gv.w);
+        sgd(v.x, b.x, gv.x); sgd(v.y, b.y, gv.y); sgd(v.z, b.z, gv.z); sgd(v.w, b.w, gv.w);
         *reinterpret_cast<float4*>(pw + sa.boff) = b;
-        v.x = fmaf(-lr, b.x, v.x); v.y = fmaf(-lr, b.y, v.y); v.z = fmaf(-lr, b.z, v.z); v.w = fmaf(-lr, b.w, v.w);
         *reinterpret_cast<float4*>(pw) = v;
         if constexpr (EMA)
           *reinterpret_cast<float4*>(pw + sa.eoff) =
@@ -781,11 +758,7 @@ __global__ void __launch_bounds__(256) img_to_nhwc4_kernel(const float* __restri
 // tail (or, unaligned, everything) element-wise.
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                    const float* __restrict__ g, size_t n, int vec, OptArgs a) {
-  if (a.flags != nullptr) {
-    const bool bad_loss = a.flags[0] != 0.f;
-    if (bad_loss && blockIdx.x == 0 && threadIdx.x == 0) a.flags[3] = 1.f;
-    if (bad_loss || a.flags[2] != 0.f) return;
-  }
+  if (opt_skip(a.flags, blockIdx.x == 0 && threadIdx.x == 0)) return;
   const AdamCoef c = adam_coef(a, (a.lr_dev != nullptr) ? a.lr_dev[0] : a.lr);
   const size_t n4 = vec ? n / 4 : 0;
   for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
@@ -822,11 +795,7 @@ __global__ void opt_tick_kernel(const float* __restrict__ flags, int* __restrict
 // the n % 4 tail (or, unaligned, everything) element-wise.
 __global__ void __launch_bounds__(256) ema_kernel(float* __restrict__ e, const float* __restrict__ p, size_t n, int vec,
                                                   OptArgs a) {
-  if (a.flags != nullptr) {
-    const bool bad_loss = a.flags[0] != 0.f;
-    if (bad_loss && blockIdx.x == 0 && threadIdx.x == 0) a.flags[3] = 1.f;
-    if (bad_loss || a.flags[2] != 0.f) return;
-  }
+  if (opt_skip(a.flags, blockIdx.x == 0 && threadIdx.x == 0)) return;
   const float w = ema_coef(a);
   const size_t n4 = vec ? n / 4 : 0;
   for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
@@ -1113,50 +1082,45 @@ extern "C" int can_scale_update(const float* flag, float* scaler, int interval, 
   return (int)hipGetLastError();
 }
 
-extern "C" int can_pack_conv(const float* w, void* fwd, void* dgr, int Co, int Ci, int taps, int first, int dt,
-                             void* stream) {
-  CAN_LAUNCH_DT(dt, pack_conv_kernel, dim3(grid_for((size_t)Co * Ci * taps, 256, 4096)),
-                dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)fwd, (bf16_t*)dgr, Co, Ci,
-                taps, first);
-  return (int)hipGetLastError();
-}
-
 extern "C" int can_img_to_nhwc4(const float* img, void* out, int N, int H, int W, int dt, void* stream) {
   CAN_LAUNCH_DT(dt, img_to_nhwc4_kernel, dim3(grid_for((size_t)N * H * W, 256, 8192)),
                 dim3(256), 0, (hipStream_t)stream, img, (uint2*)out, N, H, W);
   return (int)hipGetLastError();
 }
 
-extern "C" int can_pack_multi(const long long* desc, int layers, int max_tiles, int dt, void* stream) {
-  if (layers <= 0) return 0;
-  // grid.x covers the largest layer's 32x32 tiles (B1: 512 -> 1024 channels = 512 tiles)
-  OptArgs sa{};
-  hipStream_t s = (hipStream_t)stream;
-  if (dt == DT_F16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_F16, OPT_NONE>), dim3(max_tiles, layers), dim3(256), 0, s, desc, sa);
-  else if (dt == DT_BF16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, OPT_NONE>), dim3(max_tiles, layers), dim3(256), 0, s, desc, sa);
-  else
-    return -20;
+// The one place that maps (dt, OPT, EMA) to an instantiation of pack_multi_kernel (all 16 of them).  grid.x covers the
+// largest row's 32x32 tiles (B1: 512 -> 1024 channels = 512 tiles) or 4096-element chunks.  -20: not a 16-bit dt.
+// t1 / t2 (optimizer steps): the device counts that advance in one one-thread launch right after the step, under the
+// step's flags (nothing comes between the two launches on the host).
+static int pack_multi_launch(const long long* desc, int rows, int max_tiles, int dt, int opt, bool ema,
+                             const OptArgs& sa, hipStream_t s, int* t1 = nullptr, int* t2 = nullptr) {
+  if (dt != DT_F16 && dt != DT_BF16) return -20;
+  const dim3 grid(max_tiles, rows), blk(256);
+#define CAN_PACK_CASE(O, E)                                                                                        \
+  case 2 * O + E:                                                                                                  \
+    if (dt == DT_F16) hipLaunchKernelGGL((pack_multi_kernel<DT_F16, O, E>), grid, blk, 0, s, desc, sa);             \
+    else hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, O, E>), grid, blk, 0, s, desc, sa);                         \
+    break
+  switch (2 * opt + (ema ? 1 : 0)) {
+    CAN_PACK_CASE(OPT_NONE, false);
+    CAN_PACK_CASE(OPT_SGD, false);
+    CAN_PACK_CASE(OPT_SGD, true);
+    CAN_PACK_CASE(OPT_SGD_WD, false);
+    CAN_PACK_CASE(OPT_SGD_WD, true);
+    CAN_PACK_CASE(OPT_ADAM, false);
+    CAN_PACK_CASE(OPT_ADAM, true);
+    CAN_PACK_CASE(OPT_SWAP, false);
+    default: return -2;
+  }
+#undef CAN_PACK_CASE
+  if (t1 != nullptr || t2 != nullptr)
+    hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)sa.flags, t1, t2);
   return (int)hipGetLastError();
 }
 
-// The fused optimizer step (pack_multi_kernel<DT, OPT_SGD>): rows cover every parameter of the arena once; grad and
-// momentum arenas are at goff / boff floats from the master arena.
-extern "C" int can_sgd_pack(const long long* desc, int rows, int max_tiles, long long goff, long long boff, float lr,
-                            float momentum, float gscale, float* flags, const float* lr_dev, int dt, void* stream) {
-  if (rows <= 0) return 0;
-  OptArgs sa{};
-  sa.goff = goff; sa.boff = boff; sa.lr = lr; sa.momentum = momentum; sa.gscale = gscale;
-  sa.flags = flags; sa.lr_dev = lr_dev;
-  hipStream_t s = (hipStream_t)stream;
-  if (dt == DT_F16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_F16, OPT_SGD>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
-  else if (dt == DT_BF16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, OPT_SGD>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
-  else
-    return -20;
-  return (int)hipGetLastError();
+extern "C" int can_pack_multi(const long long* desc, int layers, int max_tiles, int dt, void* stream) {
+  if (layers <= 0) return 0;
+  return pack_multi_launch(desc, layers, max_tiles, dt, OPT_NONE, false, OptArgs{}, (hipStream_t)stream);
 }
 
 // Stand-alone Adam / AdamW over flat fp32 buffers (any n, any alignment).  t_dev: the device step count (applied steps
@@ -1195,67 +1159,27 @@ extern "C" int can_ema(float* e, const float* p, size_t n, double decay, int war
   return (int)hipGetLastError();
 }
 
-// The fused optimizer step for every optimizer: opt 1 = SGD-momentum (can_sgd_pack's kernel), 2 = SGD with coupled
-// weight decay, 3 = Adam / AdamW (mom = first moment, second moment at voff; t_dev required, advanced when applied).
-static int opt_pack_launch(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
-                           long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
-                           int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt,
-                           void* stream, const float* gmul, bool ema, long long eoff, double ema_decay, int ema_warmup,
-                           int* ema_t) {
+// The fused optimizer step for every optimizer: rows cover every parameter of the arena once; the gradient and momentum
+// arenas are at goff / boff floats from the masters.  opt 1 = SGD-momentum, 2 = SGD with coupled weight decay, 3 = Adam
+// / AdamW (mom = first moment, second moment at voff; t_dev required, advanced when applied).  eoff != 0: the EMA of
+// the parameters is updated in the same launch, its arena eoff floats from the masters, ema_t the device count of
+// applied updates (required; advanced with the step, for every optimizer); refuses a decay outside [0, 1).
+extern "C" int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
+                            long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
+                            int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt,
+                            void* stream, const float* gmul, long long eoff, double ema_decay, int ema_warmup,
+                            int* ema_t) {
+  const bool ema = eoff != 0;
   if (rows <= 0) return 0;
   if (opt < OPT_SGD || opt > OPT_ADAM || (opt == OPT_ADAM && t_dev == nullptr)) return -2;
-  if (ema && (ema_t == nullptr || eoff == 0 || !(ema_decay >= 0.0 && ema_decay < 1.0))) return -2;
-  if (dt != DT_F16 && dt != DT_BF16) return -20;
+  if (ema && (ema_t == nullptr || !(ema_decay >= 0.0 && ema_decay < 1.0))) return -2;
   OptArgs sa{};
   sa.goff = goff; sa.boff = boff; sa.voff = (opt == OPT_ADAM) ? voff : 0;
   sa.lr = lr; sa.momentum = momentum; sa.gscale = gscale; sa.wd = wd; sa.eps = eps; sa.decoupled = decoupled;
   sa.beta1 = beta1; sa.beta2 = beta2; sa.flags = flags; sa.lr_dev = lr_dev; sa.t = t_dev; sa.gmul = gmul;
-  if (ema) {
-    sa.eoff = eoff; sa.ema_decay = ema_decay; sa.ema_warmup = ema_warmup ? 1 : 0; sa.ema_t = ema_t;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(max_tiles, rows), blk(256);
-#define CAN_OPT_LAUNCH(O, E)                                                                                    \
-  do {                                                                                                           \
-    if (dt == DT_F16) hipLaunchKernelGGL((pack_multi_kernel<DT_F16, O, E>), grid, blk, 0, s, desc, sa);          \
-    else hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, O, E>), grid, blk, 0, s, desc, sa);                       \
-  } while (0)
-  if (!ema) {
-    if (opt == OPT_SGD) CAN_OPT_LAUNCH(OPT_SGD, false);
-    else if (opt == OPT_SGD_WD) CAN_OPT_LAUNCH(OPT_SGD_WD, false);
-    else CAN_OPT_LAUNCH(OPT_ADAM, false);
-  } else {
-    if (opt == OPT_SGD) CAN_OPT_LAUNCH(OPT_SGD, true);
-    else if (opt == OPT_SGD_WD) CAN_OPT_LAUNCH(OPT_SGD_WD, true);
-    else CAN_OPT_LAUNCH(OPT_ADAM, true);
-  }
-#undef CAN_OPT_LAUNCH
-  // the counts advance in one one-thread launch right after the step, under the step's flags
-  int* t1 = (opt == OPT_ADAM) ? t_dev : nullptr;
-  int* t2 = ema ? ema_t : nullptr;
-  if (t1 != nullptr || t2 != nullptr)
-    hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, s, (const float*)flags, t1, t2);
-  return (int)hipGetLastError();
-}
-
-extern "C" int can_opt_pack(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
-                            long long voff, float lr, float momentum, double beta1, double beta2, float eps, float wd,
-                            int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev, int dt,
-                            void* stream, const float* gmul) {
-  return opt_pack_launch(desc, rows, max_tiles, opt, goff, boff, voff, lr, momentum, beta1, beta2, eps, wd, decoupled,
-                         gscale, t_dev, flags, lr_dev, dt, stream, gmul, false, 0, 0.0, 0, nullptr);
-}
-
-// can_opt_pack with the EMA of the parameters updated in the same launch: the EMA arena eoff floats from the masters,
-// ema_t the device count of applied updates (required; advanced with the step, for every optimizer).  Refuses a decay
-// outside [0, 1).
-extern "C" int can_opt_pack_ema(const long long* desc, int rows, int max_tiles, int opt, long long goff, long long boff,
-                                long long voff, float lr, float momentum, double beta1, double beta2, float eps,
-                                float wd, int decoupled, float gscale, int* t_dev, float* flags, const float* lr_dev,
-                                int dt, void* stream, const float* gmul, long long eoff, double ema_decay,
-                                int ema_warmup, int* ema_t) {
-  return opt_pack_launch(desc, rows, max_tiles, opt, goff, boff, voff, lr, momentum, beta1, beta2, eps, wd, decoupled,
-                         gscale, t_dev, flags, lr_dev, dt, stream, gmul, true, eoff, ema_decay, ema_warmup, ema_t);
+  sa.eoff = eoff; sa.ema_decay = ema_decay; sa.ema_warmup = ema_warmup ? 1 : 0; sa.ema_t = ema_t;
+  return pack_multi_launch(desc, rows, max_tiles, dt, opt, ema, sa, (hipStream_t)stream,
+                           (opt == OPT_ADAM) ? t_dev : nullptr, ema ? ema_t : nullptr);
 }
 
 // The swap launch (pack_multi_kernel<DT, OPT_SWAP>): every master exchanged with its EMA copy eoff floats away, over
@@ -1265,14 +1189,7 @@ extern "C" int can_swap_pack(const long long* desc, int rows, int max_tiles, lon
   if (eoff == 0) return -2;
   OptArgs sa{};
   sa.eoff = eoff;
-  hipStream_t s = (hipStream_t)stream;
-  if (dt == DT_F16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_F16, OPT_SWAP>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
-  else if (dt == DT_BF16)
-    hipLaunchKernelGGL((pack_multi_kernel<DT_BF16, OPT_SWAP>), dim3(max_tiles, rows), dim3(256), 0, s, desc, sa);
-  else
-    return -20;
-  return (int)hipGetLastError();
+  return pack_multi_launch(desc, rows, max_tiles, dt, OPT_SWAP, false, sa, (hipStream_t)stream);
 }
 
 // The gradient-norm pass (grad_norm_partial_kernel + grad_norm_final_kernel).  tab: np {offset, count} int64 pairs on

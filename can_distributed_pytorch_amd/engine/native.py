@@ -21,7 +21,7 @@ re-designed for MI355X:
 * roctx ranges (utils/profiling.trace_range, CANNET_ROCTX=1) mark the
   forward / backward / all-reduce / optimizer phases; ``comm_timing`` records
   hipEvents around the post-backward all-reduce join (exposed comm time);
-* the SGD update and the bf16 weight packs are ONE kernel (executor.sgd_step): the packs are written from the
+* the optimizer update and the 16-bit weight packs are ONE kernel (executor.opt_step): the packs are written from the
   updated weights in registers, the 83 MB of fp32 masters are not re-read;
 * with ``graph=True`` the whole step (for a fixed input shape) is captured
   once and replayed: one graph launch per stream per step instead of ~90 kernel
@@ -205,8 +205,8 @@ class NativeStepper:
         self.mom2 = torch.zeros_like(self.arena.data) if optimizer != "sgd" else None
         self.opt_t = torch.zeros(1, dtype=torch.int32, device=self.device) if optimizer != "sgd" else None
         self.grads = self.arena.grad_views()
-        # EMA of the parameters (0 = off: no arena, and the default step keeps sgd_step): filled from the masters at
-        # the end of the constructor, once the weights are final (after the rank-0 broadcast)
+        # EMA of the parameters (0 = off: no arena, and the step launches the kernel without EMA): filled from the
+        # masters at the end of the constructor, once the weights are final (after the rank-0 broadcast)
         self.ema_decay = float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         self.ema = torch.zeros_like(self.arena.data) if self.ema_decay > 0 else None
@@ -375,17 +375,12 @@ class NativeStepper:
         if not update:
             return self.flags[1:2]
         with trace_range("cannet/sgd"):
-            # the optimizer over the arena and the 16-bit weight packs in ONE launch (executor.sgd_step / opt_step)
-            if self.optimizer == "sgd" and self.weight_decay == 0 and not clip and self.ema is None:
-                ex.sgd_step(self.arena.data, self.arena.grad, self.mom, self._lr, self.momentum, 1.0 / self.world,
-                            flags=self.flags, lr_dev=self._lr_dev)
-            else:
-                ex.opt_step(self.arena.data, self.arena.grad, self.mom, self._lr, 1.0 / self.world,
-                            optimizer=self.optimizer, momentum=self.momentum, weight_decay=self.weight_decay,
-                            betas=self.betas, eps=self.eps, mom2=self.mom2, step=self.opt_t, flags=self.flags,
-                            lr_dev=self._lr_dev, gmul=self.gn[1:2] if clip else None,
-                            **(dict(ema=self.ema, ema_t=self.ema_t, ema_decay=self.ema_decay,
-                                    ema_warmup=self.ema_warmup) if self.ema is not None else {}))
+            # the optimizer over the arena and the 16-bit weight packs in ONE launch (executor.opt_step)
+            ex.opt_step(self.arena.data, self.arena.grad, self.mom, self._lr, 1.0 / self.world,
+                        optimizer=self.optimizer, momentum=self.momentum, weight_decay=self.weight_decay,
+                        betas=self.betas, eps=self.eps, mom2=self.mom2, step=self.opt_t, flags=self.flags,
+                        lr_dev=self._lr_dev, gmul=self.gn[1:2] if clip else None, ema=self.ema, ema_t=self.ema_t,
+                        ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
             if sc is not None:
                 self.C.scale_update(self.flags.data_ptr() + 8, sc.data_ptr(), int(self.scale_interval), 2.0, 0.5,
                                     float(2 ** 24), st)

@@ -105,6 +105,9 @@ class CANNetExecutor(ContextSchedule):
         self._pack_version = None
         self._pack_desc = None          # device descriptor rows of the batched pack launch
         self._pack_desc_ptrs = None
+        self._opt_key = None            # opt_prepare: the arena and parameter addresses its rows were built for,
+        self._opt_desc = None           #   the device descriptor rows of the fused optimizer / swap launch
+        self._opt_tiles = 0             #   and its grid width
         self.ws = None
         self.last_wvalid = None         # valid width of the last forward's b6 when it was width-padded
         self._ws_need = {}              # (n, h, w, dispatch config) -> weight-gradient workspace floats
@@ -191,61 +194,20 @@ class CANNetExecutor(ContextSchedule):
         self.C.pack_multi(self._pack_desc.data_ptr(), self._pack_desc.shape[0], self._pack_tiles, self.dt, st)
         self._pack_version = ver
 
-    def sgd_step(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor, lr: float, momentum: float,
-                 gscale: float, flags: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None):
-        """The fused optimizer step (elementwise.hip pack_multi_kernel<DT, true>): SGD-momentum (torch.optim.SGD
-        semantics, bit for bit the sgd_momentum kernel) over every parameter of the flat arena ``data`` (gradients /
-        momentum in the same layout in ``grad`` / ``mom``) and the 16-bit packs written from the updated weights, in
-        ONE launch: the packs no longer re-read the 83 MB of fp32 masters.  flags / lr_dev: the native step's device
-        flag vector (a non-finite loss or gradient skips the step, weights and packs untouched) and learning rate."""
-        desc, rows, tiles, goff, boff = self.sgd_prepare(data, grad, mom)
-        self.C.sgd_pack(desc, rows, tiles, goff, boff, float(lr), float(momentum), float(gscale),
-                        flags.data_ptr() if flags is not None else 0, lr_dev.data_ptr() if lr_dev is not None else 0,
-                        self.dt, self._stream())
-        self._pack_version = self._weights_version()
-
-    def sgd_prepare(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor):
-        """The fused optimizer's descriptor rows for this arena (built once: call before a graph capture, the
-        build copies them to the device)."""
-        if not self.packs:
-            self._alloc_packs(self.head.weight.device)
-        params = self._params()
-        base, esz = data.data_ptr(), data.element_size()
-        for p in params:
-            if not (p.dtype == torch.float32 and p.is_contiguous() and
-                    base <= p.data_ptr() < base + data.numel() * esz):
-                raise ValueError("sgd_step: every parameter must be a contiguous fp32 view of the arena")
-        if grad.shape != data.shape or mom.shape != data.shape or grad.dtype != torch.float32 or \
-                mom.dtype != torch.float32:
-            raise ValueError("sgd_step: grad / momentum arenas must match the parameter arena")
-        key = (base, tuple(p.data_ptr() for p in params))
-        if getattr(self, "_sgd_key", None) != key:
-            rows = self._pack_rows()
-            packed = {r[0] for r in rows}
-            for p in params:
-                if p.data_ptr() not in packed:           # biases, head, conv{S}_1: SGD only
-                    rows.append([p.data_ptr(), 0, 0, 0, 0, 0, 0, -1, 0, 0, 0, p.numel()])
-            if sorted(r[0] for r in rows) != sorted(p.data_ptr() for p in params):
-                raise RuntimeError("sgd_step: the descriptor rows do not cover every parameter exactly once")
-            self._sgd_desc = torch.tensor(rows, dtype=torch.int64, device=data.device)
-            self._sgd_tiles = max(((r[3] + 31) // 32) * ((r[4] + 31) // 32) if r[7] >= 0 else -(-r[11] // 4096)
-                                  for r in rows)
-            self._sgd_key = key
-        if (grad.data_ptr() - base) % esz or (mom.data_ptr() - base) % esz:
-            raise ValueError("sgd_step: arena offsets must be whole floats")
-        return (self._sgd_desc.data_ptr(), self._sgd_desc.shape[0], self._sgd_tiles,
-                (grad.data_ptr() - base) // esz, (mom.data_ptr() - base) // esz)
-
     def opt_step(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor, lr: float, gscale: float,
                  optimizer: str = "sgd", momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999),
                  eps: float = 1e-8, mom2: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None,
                  flags: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None,
                  gmul: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None,
                  ema_t: Optional[torch.Tensor] = None, ema_decay: float = 0.0, ema_warmup: bool = True):
-        """The fused optimizer step for every optimizer (elementwise.hip pack_multi_kernel<DT, OPT>), ONE launch over
-        the arena that also writes the 16-bit packs, as ``sgd_step``: ``optimizer`` = "sgd" (torch.optim.SGD with
-        momentum and coupled ``weight_decay``; weight decay 0 runs sgd_step's kernel), "adam" (torch.optim.Adam,
-        coupled weight decay) or "adamw" (decoupled).  Adam: ``mom`` / ``mom2`` are the first / second moment arenas
+        """The fused optimizer step (elementwise.hip pack_multi_kernel<DT, OPT, EMA>): the update over every parameter
+        of the flat arena ``data`` (gradients / momentum in the same layout in ``grad`` / ``mom``) and the 16-bit packs
+        written from the updated weights, in ONE launch: the packs do not re-read the 83 MB of fp32 masters.
+        ``optimizer`` = "sgd" (torch.optim.SGD with momentum, bit for bit the sgd_momentum kernel, and coupled
+        ``weight_decay``, its own instantiation when not 0), "adam" (torch.optim.Adam,
+        coupled weight decay) or "adamw" (decoupled).  flags / lr_dev: the native step's device flag vector (a
+        non-finite loss or gradient skips the step, weights and packs untouched) and learning rate.
+        Adam: ``mom`` / ``mom2`` are the first / second moment arenas
         and ``step`` the int32 device count of applied steps, which a one-thread launch after the step advances
         unless the step was skipped through ``flags``.  ``gmul``: an fp32 device scalar the kernel multiplies into
         ``gscale`` (one fp32 product: the clip coefficient of ``grad_norm``).  ``ema``: an fp32 arena like ``data``
@@ -273,9 +235,8 @@ class CANNetExecutor(ContextSchedule):
                         float(betas[1]), float(eps), float(weight_decay), int(optimizer == "adamw"), float(gscale),
                         step.data_ptr() if adam else 0, flags.data_ptr() if flags is not None else 0,
                         lr_dev.data_ptr() if lr_dev is not None else 0, self.dt, self._stream(),
-                        gmul.data_ptr() if gmul is not None else 0,
-                        **(dict(eoff=eoff, ema_decay=float(ema_decay), ema_warmup=int(bool(ema_warmup)),
-                                ema_t=ema_t.data_ptr()) if ema is not None else {}))
+                        gmul.data_ptr() if gmul is not None else 0, eoff, float(ema_decay), int(bool(ema_warmup)),
+                        ema_t.data_ptr() if ema is not None else 0)
         self._pack_version = self._weights_version()
 
     def swap_weights(self, data: torch.Tensor, ema: torch.Tensor):
@@ -283,12 +244,11 @@ class CANNetExecutor(ContextSchedule):
         16-bit pack from the values that land in the master slots.  The parameters are views of ``data``, so the model
         now holds (evaluates, saves) the other set of weights; no address changes, so captured graphs stay valid.  Two
         swaps in a row are the identity, packs included."""
-        if not getattr(self, "_sgd_key", None) or self._sgd_key[0] != data.data_ptr():
+        if self._opt_key is None or self._opt_key[0] != data.data_ptr():
             raise RuntimeError("swap_weights: call opt_prepare on this arena first")
-        eoff = self._arena_off(data, ema, "EMA")
-        self.C.swap_pack(self._sgd_desc.data_ptr(), self._sgd_desc.shape[0], self._sgd_tiles, eoff, self.dt,
-                         self._stream())
-        self.mark_weights_updated()
+        self.C.swap_pack(self._opt_desc.data_ptr(), self._opt_desc.shape[0], self._opt_tiles,
+                         self._arena_off(data, ema, "EMA"), self.dt, self._stream())
+        self._pack_version = self._weights_version()
 
     def norm_prepare(self, grad: torch.Tensor, slots: Sequence):
         """The gradient-norm pass's device table and scratch for this gradient arena (elementwise.hip
@@ -333,16 +293,34 @@ class CANNetExecutor(ContextSchedule):
 
     def opt_prepare(self, data: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor,
                     mom2: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None):
-        """sgd_prepare (the descriptor rows are shared) + the second-moment and the EMA arena's offsets (0 without
-        one)."""
-        desc, rows, tiles, goff, boff = self.sgd_prepare(data, grad, mom)
-        voff = self._arena_off(data, mom2, "second-moment") if mom2 is not None else 0
-        eoff = self._arena_off(data, ema, "EMA") if ema is not None else 0
-        return desc, rows, tiles, goff, boff, voff, eoff
-
-    def mark_weights_updated(self):
-        """Called by the fused optimizer after it has re-packed (keeps versions in sync)."""
-        self._pack_version = self._weights_version()
+        """The fused optimizer's launch arguments for these arenas: (descriptor rows' device pointer, row count, grid
+        width, then the gradient / momentum / second-moment / EMA arena's offset from ``data`` in floats, 0 without
+        one).  The parameters are validated and the rows built once per layout of the masters (call before a graph
+        capture: the build copies the rows to the device): a repeated call compares the addresses of ``data`` and of
+        every parameter, so a moved one is still noticed, and checks the four arenas against ``data``."""
+        key = (data.data_ptr(), data.numel(), tuple(p.data_ptr() for p in self._plist))
+        if key != self._opt_key:
+            if not self.packs:
+                self._alloc_packs(self.head.weight.device)
+            base, end = key[0], key[0] + key[1] * data.element_size()
+            for p in self._plist:
+                if not (p.dtype == torch.float32 and p.is_contiguous() and base <= p.data_ptr() < end):
+                    raise ValueError("opt_prepare: every parameter must be a contiguous fp32 view of the arena")
+            rows = self._pack_rows()
+            packed = {r[0] for r in rows}
+            for p in self._plist:
+                if p.data_ptr() not in packed:           # biases, head, conv{S}_1: no pack
+                    rows.append([p.data_ptr(), 0, 0, 0, 0, 0, 0, -1, 0, 0, 0, p.numel()])
+            if sorted(r[0] for r in rows) != sorted(key[2]):
+                raise RuntimeError("opt_prepare: the descriptor rows do not cover every parameter exactly once")
+            self._opt_desc = torch.tensor(rows, dtype=torch.int64, device=data.device)
+            self._opt_tiles = max(((r[3] + 31) // 32) * ((r[4] + 31) // 32) if r[7] >= 0 else -(-r[11] // 4096)
+                                  for r in rows)
+            self._opt_key = key
+        return (self._opt_desc.data_ptr(), self._opt_desc.shape[0], self._opt_tiles,
+                self._arena_off(data, grad, "gradient"), self._arena_off(data, mom, "momentum"),
+                self._arena_off(data, mom2, "second-moment") if mom2 is not None else 0,
+                self._arena_off(data, ema, "EMA") if ema is not None else 0)
 
     def _stream(self):
         return self.stream_override if self.stream_override is not None else _ext.stream_ptr(self.head.weight.device)

@@ -70,7 +70,8 @@ def kernel_arms(args):
 
     # arm: (launch, bytes moved, device launches per call, note)
     arms = {
-        "sgd": (lambda: ex.sgd_step(arena.data, arena.grad, mom, 1e-9, 0.95, 1.0, **common), fused_bytes(1), 1, ""),
+        "sgd": (lambda: ex.opt_step(arena.data, arena.grad, mom, 1e-9, 1.0, optimizer="sgd", **common),
+                fused_bytes(1), 1, ""),
         "sgd_wd": (lambda: ex.opt_step(arena.data, arena.grad, mom, 1e-9, 1.0, optimizer="sgd", weight_decay=5e-4,
                                        **common), fused_bytes(1), 1, ""),
         "adam": (lambda: ex.opt_step(arena.data, arena.grad, mom, 1e-9, 1.0, optimizer="adam", mom2=mom2, step=t,

@@ -326,8 +326,8 @@ def test_weight_packs_bitwise(arena):
 
 @pytest.mark.parametrize("offset", [0, 1])
 def test_fused_sgd_pack_matches_two_launch_step(offset):
-    """The fused optimizer step (executor.sgd_step: SGD-momentum over every arena parameter + the 16-bit packs from
-    the updated weights, one launch) == sgd_momentum over the arena followed by pack_multi, bit for bit: weights,
+    """The fused optimizer step (executor.opt_step, plain SGD: SGD-momentum over every arena parameter + the 16-bit
+    packs from the updated weights, one launch) == sgd_momentum over the arena followed by pack_multi, bit for bit: weights,
     momentum, every layer's fwd / dgrad pack and the interleaved context packs.  offset 1: masters / grads / momentum
     not 16-B aligned (element-wise paths).  A step flagged non-finite leaves everything untouched and latches
     flags[3]."""
@@ -379,7 +379,7 @@ def test_fused_sgd_pack_matches_two_launch_step(offset):
         data.copy_(d0)
         mom.copy_(m0)
     ex.refresh_packs(force=True)
-    ex.sgd_step(data, grad, mom, 1.0, 0.95, 0.5, flags=flags, lr_dev=lr_dev)
+    ex.opt_step(data, grad, mom, 1.0, 0.5, optimizer="sgd", momentum=0.95, flags=flags, lr_dev=lr_dev)
     torch.cuda.synchronize()
     got = snapshot()
     for i, (g, r) in enumerate(zip(got, ref)):
@@ -388,8 +388,14 @@ def test_fused_sgd_pack_matches_two_launch_step(offset):
         assert torch.equal(g, r), i
     # non-finite flag: the step is skipped (weights, momentum, packs) and the sticky flag latched
     before = snapshot()
+    desc = ex._opt_desc.data_ptr()
     flags[0] = 1.0
-    ex.sgd_step(data, grad, mom, 1.0, 0.95, 0.5, flags=flags, lr_dev=lr_dev)
+    ex.opt_step(data, grad, mom, 1.0, 0.5, optimizer="sgd", momentum=0.95, flags=flags, lr_dev=lr_dev)
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(snapshot(), before))
     assert float(flags[3]) == 1.0
+    # the repeated step on the same arenas reused the descriptor rows; a parameter moved out of the arena is refused
+    assert ex._opt_desc.data_ptr() == desc
+    ps[-1].data = ps[-1].data.clone()
+    with pytest.raises(ValueError, match="view of the arena"):
+        ex.opt_step(data, grad, mom, 1.0, 0.5, optimizer="sgd", momentum=0.95, flags=flags, lr_dev=lr_dev)

@@ -1,5 +1,5 @@
-"""The fused optimizer-and-pack launches (elementwise.hip pack_multi_kernel: C.pack_multi, C.sgd_pack, C.opt_pack with
-and without EMA, C.swap_pack) bit for bit against the numpy model of tests/optpack_reference.py, on descriptor tables
+"""The fused optimizer-and-pack launches (elementwise.hip pack_multi_kernel: C.pack_multi, C.opt_pack with and without
+EMA, C.swap_pack) bit for bit against the numpy model of tests/optpack_reference.py, on descriptor tables
 built by hand: no CANNet, no executor.
 
 One table of about 150 k floats holds whole tiles (the float4 path, nine Adam-loop iterations per thread), the
@@ -18,6 +18,8 @@ Per launch kind, element type and layout:
   5. with flags[0] or flags[2] set nothing changes, no count advances, flags[3] latches only for flags[0];
   6. two swaps restore everything;
   7. a second step from the first step's result (learning rate from the device, a gradient multiplier) matches too.
+     The kind "sgd_nogmul" is the plain SGD launch of the default training step: C.opt_pack with opt = OPT_SGD and no
+     gradient multiplier on either step, so its step 2 takes the non-power-of-two gscale alone.
 (1, 2 and 4 are one comparison of the whole fp32 buffer, 3 and 4 one of the whole pack buffer.)
 
 Adam's p is held bit for bit like the rest: the kernel's divide and square root are the correctly rounded ones (HIP's
@@ -41,7 +43,7 @@ GSCALE2 = 0.01                          #   and a gradient scale that is no powe
                                         #   g * (gscale * gmul) then round differently, only the second is right
 BETAS, EPS, EMA_DECAY = (0.9, 0.999), 1e-8, 0.999
 OPT_KINDS = ("sgd", "sgd_wd", "adam", "adamw")
-KINDS = ("pack", "sgd_pack") + OPT_KINDS + tuple(k + "+ema" for k in OPT_KINDS) + ("swap",)
+KINDS = ("pack", "sgd_nogmul") + OPT_KINDS + tuple(k + "+ema" for k in OPT_KINDS) + ("swap",)
 DTS = ((R.DT_F16, "fp16"), (R.DT_BF16, "bf16"))
 
 
@@ -64,11 +66,11 @@ def _chain(kind):
     """Slot values before, after step 1 (host learning rate) and after step 2 (device learning rate, and a gradient
     multiplier where the entry point takes one): computed once, the same in every layout and element type."""
     base, _, ema = kind.partition("+")
-    emu = "sgd" if base == "sgd_pack" else base
+    emu = "sgd" if base == "sgd_nogmul" else base
     v0 = R.initial_values()
     v1 = R.apply_launch(v0, emu, t=T0, ema=bool(ema), ema_n=EMA_N0, ema_decay=EMA_DECAY, betas=BETAS, eps=EPS)
     v2 = R.apply_launch(v1, emu, t=T0 + 1, ema=bool(ema), ema_n=EMA_N0 + 1, ema_decay=EMA_DECAY, betas=BETAS, eps=EPS,
-                        lr=LR_DEV, gscale=GSCALE2, gmul=None if base == "sgd_pack" else GMUL)
+                        lr=LR_DEV, gscale=GSCALE2, gmul=None if base == "sgd_nogmul" else GMUL)
     return v0, v1, v2
 
 
@@ -113,17 +115,15 @@ class Dev:
             C.pack_multi(self.pdesc.data_ptr(), self.pdesc.shape[0], tb.pack_tiles, self.dt, _stream())
         elif base == "swap":
             C.swap_pack(self.desc.data_ptr(), self.desc.shape[0], tb.max_tiles, tb.eoff, self.dt, _stream())
-        elif base == "sgd_pack":
-            C.sgd_pack(self.desc.data_ptr(), self.desc.shape[0], tb.max_tiles, tb.goff, tb.boff, R.LR, R.MOMENTUM,
-                       gscale, self.flags.data_ptr(), lr_dev, self.dt, _stream())
         else:
-            opt = {"sgd": R.OPT_SGD, "sgd_wd": R.OPT_SGD_WD, "adam": R.OPT_ADAM, "adamw": R.OPT_ADAM}[base]
-            wd = 0.0 if base == "sgd" else R.WD
+            opt = {"sgd_nogmul": R.OPT_SGD, "sgd": R.OPT_SGD, "sgd_wd": R.OPT_SGD_WD, "adam": R.OPT_ADAM,
+                   "adamw": R.OPT_ADAM}[base]
+            wd = 0.0 if opt == R.OPT_SGD else R.WD
             kw = dict(eoff=tb.eoff, ema_decay=EMA_DECAY, ema_warmup=1, ema_t=self.ema_t.data_ptr()) if ema else {}
             C.opt_pack(self.desc.data_ptr(), self.desc.shape[0], tb.max_tiles, opt, tb.goff, tb.boff, tb.voff, R.LR,
                        R.MOMENTUM, BETAS[0], BETAS[1], EPS, wd, int(base == "adamw"), gscale,
                        self.t.data_ptr() if opt == R.OPT_ADAM else 0, self.flags.data_ptr(), lr_dev, self.dt,
-                       _stream(), self.gmul.data_ptr() if step2 else 0, **kw)
+                       _stream(), self.gmul.data_ptr() if step2 and base != "sgd_nogmul" else 0, **kw)
 
 
 def _check(dev, want32, want16, what):
@@ -194,7 +194,7 @@ def test_repack_reproduces_the_optimizers_packs():
     layout that sends every tile down the element-wise path, C.pack_multi from the stored masters rewrites every
     pack with the bytes the step wrote."""
     table = _table("all_off1")
-    for kind in ("sgd_pack", "sgd+ema", "sgd_wd", "adam"):
+    for kind in ("sgd_nogmul", "sgd+ema", "sgd_wd", "adam"):
         dev = Dev(table, R.DT_F16)
         dev.launch(kind)
         a32, a16 = dev.get()

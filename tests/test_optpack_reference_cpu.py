@@ -283,7 +283,7 @@ def test_expected_buffers(layout):
 @pytest.mark.parametrize("layout", R.LAYOUTS)
 def test_table_layout(layout):
     """The builder's own promises: slots and packs disjoint with sentinels between, the alignments each layout names,
-    max_tiles as the executor's sgd_prepare computes it."""
+    max_tiles as the executor's opt_prepare computes it."""
     t = R.Table(layout)
     buf32, buf16 = t.initial()
     used = np.zeros(t.total32, dtype=np.int32)
