@@ -30,6 +30,7 @@
 //     sharing one pixel tile (and its halo) run on the same XCD / L2.
 #include "api.h"
 #include "common.h"
+#include "conv_epilogue.h"
 #include "conv_plan.h"
 #include "fastdiv.h"
 #include <stdlib.h>
@@ -53,32 +54,33 @@ struct ConvArgs {
 // not > 0 (the ReLU mask of the pool input).  uint32 codes[N][H/2][W/2][C/8], channel c in word c/8,
 // nibble c%8.  That is everything the backward needs, so the full-resolution pre-pool activation
 // (805 MB for conv1_2 at batch 8 x 768 x 1024) is never written nor re-read.
-// EPI_POOLBWD (LDS-DMA kernels only): the GEMM output is the gradient of a 2x2/s2 max-pool output; the
-// epilogue scatters it straight into the pool INPUT gradient through the codes (a.pcodes, pooled
-// resolution) into a.y [N][2H][2W][Cout].
-// EPI_POOLFWD (LDS-DMA v2 kernel only, H even, W % (TP/2) == 0): bias + ReLU like EPI_BIAS_RELU, and
-// the 2x2/s2 max-pool of the result is written to a.yp [N][H/2][W/2][Cout] in the same epilogue.  A pixel
-// tile is then 2 image rows x TP/2 columns with the rows interleaved inside each 16-pixel MFMA fragment
-// (fragment f, row fr: column f*8 + fr/2, row fr&1), so every pool window sits in 4 adjacent lanes and is
-// reduced with two DPP quad permutes (the pooled map is never re-read from HBM by a separate pass).
-// EPI_F32 (LDS-DMA kernels only): the raw GEMM result (+ bias when a.bias is given) stored as fp32 into
-// a.y reinterpreted as float [M][Cout] — the split-bf16 fp32 path (ops/fp32.py) sums hi*hi + hi*lo + lo*hi
-// in one K-concatenated GEMM and needs the fp32 accumulator, not its 16-bit rounding.
-// EPI_CTXF / EPI_CTXB (LDS-DMA v2 kernel, 256 x 256 tiles, 1x1): the context module as ONE GEMM each way,
-// see "Linearised context module" below.
+// EPI_POOLBWD: the GEMM output is the gradient of a 2x2/s2 max-pool output; the epilogue scatters it straight
+// into the pool INPUT gradient through the codes (a.pcodes, pooled resolution) into a.y [N][2H][2W][Cout].
+// EPI_POOLFWD (H even, W a multiple of the tile's columns): bias + ReLU like EPI_BIAS_RELU, and the 2x2/s2
+// max-pool of the result is written to a.yp [N][H/2][W/2][Cout] in the same epilogue (the pooled map is never
+// re-read from HBM by a separate pass).  LDS-DMA v2 kernel: a pixel tile is 2 image rows x TP/2 columns with the
+// rows interleaved inside each 16-pixel MFMA fragment (fragment f, row fr: column f*8 + fr/2, row fr&1), so every
+// pool window sits in 4 adjacent lanes and is reduced with two DPP quad permutes; the row ring's 2 x 128 tiles the
+// same with their own lane order (tile_pix); the halo and ws64 kernels stage their 4 x 64 tile in LDS
+// (conv_epilogue.h pool_staged_store).
+// EPI_F32: the raw GEMM result (+ bias when a.bias is given) stored as fp32 into a.y reinterpreted as float
+// [M][Cout] — the split-bf16 fp32 path (ops/fp32.py) sums hi*hi + hi*lo + lo*hi in one K-concatenated GEMM and
+// needs the fp32 accumulator, not its 16-bit rounding.
+// EPI_CTXF / EPI_CTXB (1x1): the context module as ONE GEMM each way, see "Linearised context module" below.
 // The EPI_* enum (and the sign-bit layout of EPI_MASKB) is in conv_plan.h.
+//
+// Which family runs which epilogue (what plan_conv may pick: the caps column of kTileCfgs in conv_plan.h is the
+// record for the pooling, sign-bit and padded-width ones):
+//   conv_igemm_kernel (1-4)         BIAS_RELU, MASK, NONE, BIAS, SIGMOID; the Cin = 3 load: BIAS_RELU
+//   conv_glds_kernel (11-13)        the same + POOLBWD, F32 (launch_tile also instantiates it with POOLFWD, which its
+//                                   main loop's linear pixel order does not serve: never planned)
+//   conv_glds2_kernel (21-23, 25)   the same + MASKB, POOLFWD; (21, 24) CTXF, CTXB
+//   conv_rring_kernel (27-29)       BIAS_RELU, MASK, NONE, BIAS, POOLBWD, F32; 2-row tiles (27, 29): POOLFWD
+//   conv_halo64_kernel (31)         BIAS_RELU (+ sign bits out), MASK, NONE, BIAS; 64 channels x 64 columns: POOLFWD
+//   conv_ws64_kernel (33)           BIAS_RELU, MASK (16-bit map or sign bits, + W1G), NONE, BIAS, POOLFWD
+//   conv_first_halo_kernel (32)     BIAS_RELU (+ sign bits out)
+// The per-pixel steps they share (bias, activation, ReLU masks, sign bits, pool max / codes) are in conv_epilogue.h.
 
-// sign bits of 8 consecutive 16-bit values (two per 32-bit word, low half first): bit k = value k > 0
-__device__ __forceinline__ unsigned sign_bits8(unsigned w0, unsigned w1, unsigned w2, unsigned w3) {
-  const unsigned w[4] = {w0, w1, w2, w3};
-  unsigned b = 0u;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    b |= (pos_bits((unsigned short)(w[k] & 0xFFFFu)) ? 1u : 0u) << (2 * k);
-    b |= (pos_bits((unsigned short)(w[k] >> 16)) ? 1u : 0u) << (2 * k + 1);
-  }
-  return b;
-}
 enum { LOAD_GENERIC = 0, LOAD_FIRST = 1 };
 
 
@@ -229,68 +231,50 @@ conv_igemm_kernel(ConvArgs a) {
 
   // ---- epilogue: lane owns channels [chb, chb+16) of one pixel per tile i
   const int chb = ct * TC + wc * 64 + fq * 16;
+  constexpr bool BIASED = (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS);
   float bias[16];
-  if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD) {
-#pragma unroll
-    for (int c = 0; c < 16; c += 4) {
-      const float4 b4 = *reinterpret_cast<const float4*>(a.bias + chb + c);
-      bias[c] = b4.x; bias[c + 1] = b4.y; bias[c + 2] = b4.z; bias[c + 3] = b4.w;
-    }
-  }
+  if (BIASED) load_bias<16>(bias, a.bias + chb);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int m = pt * TP + wp * 64 + i * 16 + fr;
     if (m >= a.M) continue;
     float v[16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[j * 4 + r] = acc[j][i][r];
-    if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD) {
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        v[c] += bias[c];
-        if (EPI != EPI_BIAS) v[c] = fmaxf(v[c], 0.f);
-      }
-    }
-    if (EPI == EPI_SIGMOID) {
-#pragma unroll
-      for (int c = 0; c < 16; ++c) v[c] = 1.f / (1.f + __expf(-v[c]));
-    }
+    frag_values(v, acc, i);
+    if (BIASED) bias_act<EPI, 16>(v, bias, true);
+    if (EPI == EPI_SIGMOID) sigmoid<16>(v);
     const size_t off = (size_t)m * a.Cout + chb;
     if (EPI == EPI_MASK) {
       const uint4 m0 = *reinterpret_cast<const uint4*>(a.mask + off);
       const uint4 m1 = *reinterpret_cast<const uint4*>(a.mask + off + 8);
       const unsigned mw[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const unsigned short bits = (unsigned short)(mw[c >> 1] >> ((c & 1) * 16));
-        const bool pos = pos_bits(bits);
-        v[c] = pos ? v[c] : 0.f;
-      }
+      relu_mask16<16, false>(v, mw, nullptr);
     }
-    uint4 o0 = make_uint4(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], v[3]), pack2<DT>(v[4], v[5]), pack2<DT>(v[6], v[7]));
-    uint4 o1 = make_uint4(pack2<DT>(v[8], v[9]), pack2<DT>(v[10], v[11]), pack2<DT>(v[12], v[13]), pack2<DT>(v[14], v[15]));
-    *reinterpret_cast<uint4*>(a.y + off) = o0;
-    *reinterpret_cast<uint4*>(a.y + off + 8) = o1;
+    *reinterpret_cast<uint4*>(a.y + off) = pack8h<DT>(v);
+    *reinterpret_cast<uint4*>(a.y + off + 8) = pack8h<DT>(v + 8);
   }
+}
+
+// Launch with dynamic LDS: raise the kernel's MaxDynamicSharedMemorySize when this launch needs more than any before
+// it, launch, return the launch error.  attr_lds is the calling launcher's own static, one per
+// kernel instantiation: kernels of one signature share a function type, so a static in here would be shared by them
+template <class K, class A>
+static int launch_lds(K kfn, size_t& attr_lds, dim3 grid, int nt, size_t lds, hipStream_t s, const A& a) {
+  if (lds > attr_lds) {
+    CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr_lds = lds;
+  }
+  hipLaunchKernelGGL(kfn, grid, dim3(nt), lds, s, a);
+  return (int)hipGetLastError();
 }
 
 template <int DT, int WC, int WP, int LOAD, int EPI>
 static int launch_conv(const ConvArgs& a, hipStream_t s) {
-  constexpr int NT = 64 * WC * WP;
   constexpr int TC = 64 * WC, TP = 64 * WP;
-  const size_t lds = 2 * (TC + TP) * 128;
-  auto kfn = conv_igemm_kernel<DT, WC, WP, LOAD, EPI>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  static size_t attr_lds = 0;
   const int nct = a.Cout / TC;
   const int npt = (a.M + TP - 1) / TP;
-  hipLaunchKernelGGL(kfn, dim3(nct * npt), dim3(NT), lds, s, a);
-  return (int)hipGetLastError();
+  return launch_lds(conv_igemm_kernel<DT, WC, WP, LOAD, EPI>, attr_lds, dim3(nct * npt), 64 * WC * WP,
+                    2 * (TC + TP) * 128, s, a);
 }
 
 template <int DT, int LOAD, int EPI>
@@ -390,40 +374,6 @@ __device__ __forceinline__ int tile_pix(const ConvArgs2& a, int pt, int r) {
   }
 }
 
-// two 16-bit lanes per VGPR (the max-pool epilogue works on the stored bf16 / fp16 bit patterns: after the ReLU they
-// are non-negative, where the unsigned order of the bits is the order of the values)
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ unsigned pk_sub_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_sub_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ unsigned pk_lshl_b16(unsigned v, unsigned sh) {
-  unsigned r;
-  asm("v_pk_lshlrev_b16 %0, %1, %2" : "=v"(r) : "v"(sh), "v"(v));
-  return r;
-}
-__device__ __forceinline__ unsigned pk_mul_lo_u16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// per 16-bit half: v >> sh (arithmetic), shift amounts from the halves of sh
-__device__ __forceinline__ unsigned pk_ashr_i16(unsigned v, unsigned sh) {
-  unsigned r;
-  asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(r) : "v"(sh), "v"(v));
-  return r;
-}
-
 // Shared epilogue of the LDS-DMA kernels: lane (fr, fq) of wave (wc, wp) owns
 // 16 consecutive output channels of one pixel per 16x16 pixel fragment.
 template <int DT, int WC, int WP, int PW, int EPI, int RT = 0, bool RG = false>
@@ -431,14 +381,9 @@ __device__ __forceinline__ void glds_epilogue(const ConvArgs2& a, f32x4 (&acc)[4
                                               int wc, int wp, int fr, int fq) {
   constexpr int TC = 64 * WC, TP = 64 * PW * WP;
   const int chb = ct * TC + wc * 64 + fq * 16;
+  constexpr bool BIASED = (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD);
   float bias[16];
-  if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD || (EPI == EPI_F32 && a.bias != nullptr)) {
-#pragma unroll
-    for (int c = 0; c < 16; c += 4) {
-      const float4 b4 = *reinterpret_cast<const float4*>(a.bias + chb + c);
-      bias[c] = b4.x; bias[c + 1] = b4.y; bias[c + 2] = b4.z; bias[c + 3] = b4.w;
-    }
-  }
+  if (BIASED || (EPI == EPI_F32 && a.bias != nullptr)) load_bias<16>(bias, a.bias + chb);
   constexpr bool BPART = (EPI == EPI_MASK || EPI == EPI_MASKB || EPI == EPI_POOLBWD);
   float bs[16];
 #pragma unroll
@@ -480,6 +425,7 @@ __device__ __forceinline__ void glds_epilogue(const ConvArgs2& a, f32x4 (&acc)[4
     const int m = tile_pix<TP, EPI, RT, RG>(a, pt, wp * 64 * PW + i * 16 + fr);
     if (m >= a.M) continue;
     float v[16];
+    // (frag_values here sends the EPI_POOLBWD and EPI_F32 instantiations into scratch: 144 / 272 bytes per lane)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -519,20 +465,12 @@ __device__ __forceinline__ void glds_epilogue(const ConvArgs2& a, f32x4 (&acc)[4
       }
       continue;
     }
-    if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD) {
+    if (BIASED) {
       // padding columns of a width-padded map stay zero (every 2x2 pool window is wholly inside or outside)
       const bool cv = a.wv >= a.W || m - (int)fdiv((uint32_t)m, a.fdW) * a.W < a.wv;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        v[c] += bias[c];
-        if (EPI != EPI_BIAS) v[c] = fmaxf(v[c], 0.f);
-        v[c] = cv ? v[c] : 0.f;
-      }
+      bias_act<EPI, 16>(v, bias, cv);
     }
-    if (EPI == EPI_SIGMOID) {
-#pragma unroll
-      for (int c = 0; c < 16; ++c) v[c] = 1.f / (1.f + __expf(-v[c]));
-    }
+    if (EPI == EPI_SIGMOID) sigmoid<16>(v);
     const size_t off = (size_t)m * a.Cout + chb;
     if constexpr (EPI == EPI_F32) {
       if (a.bias != nullptr) {
@@ -547,6 +485,7 @@ __device__ __forceinline__ void glds_epilogue(const ConvArgs2& a, f32x4 (&acc)[4
     if constexpr (EPI == EPI_MASK) {
       const uint4 m0 = mk0[i], m1 = mk1[i];
       const unsigned mw[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+      // (relu_mask16<16, true> compiles to other code here, and the 128-channel data gradients measured 1 % slower)
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
         const unsigned short bits = (unsigned short)(mw[c >> 1] >> ((c & 1) * 16));
@@ -555,18 +494,8 @@ __device__ __forceinline__ void glds_epilogue(const ConvArgs2& a, f32x4 (&acc)[4
         bs[c] += v[c];
       }
     }
-    if constexpr (EPI == EPI_MASKB) {
-      const unsigned mb = mkb[i];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        v[c] = ((mb >> c) & 1u) ? v[c] : 0.f;
-        bs[c] += v[c];
-      }
-    }
-    const uint4 o0 =
-        make_uint4(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], v[3]), pack2<DT>(v[4], v[5]), pack2<DT>(v[6], v[7]));
-    const uint4 o1 =
-        make_uint4(pack2<DT>(v[8], v[9]), pack2<DT>(v[10], v[11]), pack2<DT>(v[12], v[13]), pack2<DT>(v[14], v[15]));
+    if constexpr (EPI == EPI_MASKB) relu_mask_bits<16, true>(v, mkb[i], bs);
+    const uint4 o0 = pack8h<DT>(v), o1 = pack8h<DT>(v + 8);
     if (EPI != EPI_POOLFWD || a.y != nullptr) {
       *reinterpret_cast<uint4*>(a.y + off) = o0;
       *reinterpret_cast<uint4*>(a.y + off + 8) = o1;
@@ -909,11 +838,7 @@ __device__ __forceinline__ void ctxb_epilogue(const ConvArgs2& a, f32x4 (&acc)[4
         add_bin(bo + (jB >= 0 ? jB : jA), jB >= 0 ? 1.f : 0.f);
       }
       const unsigned mw[8] = {k0[ii].x, k0[ii].y, k0[ii].z, k0[ii].w, k1[ii].x, k1[ii].y, k1[ii].z, k1[ii].w};
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const unsigned short bits = (unsigned short)(mw[c >> 1] >> ((c & 1) * 16));
-        v[c] = pos_bits(bits) ? v[c] : 0.f;
-      }
+      relu_mask16<16, false>(v, mw, nullptr);
       bf16_t* yo = a.y + (size_t)m * a.Cout + chb;
       *reinterpret_cast<uint4*>(yo) = pack8h<DT>(v);
       *reinterpret_cast<uint4*>(yo + 8) = pack8h<DT>(v + 8);
@@ -1419,17 +1344,12 @@ static int launch_glds2(const ConvArgs2& a, hipStream_t s, int ks = 1, int nb = 
     if (b.ctx_prologue) lds += tab;
     else if ((size_t)ctx_tab_row_bytes(EPI, TC) * ctx_max_rows(TP, a.W) > lds) return -15;
   }
-  auto kfn = conv_glds2_kernel<DT, WC, WP, PW, EPI>;
   static size_t attr_lds = 0;
-  if (lds > attr_lds) {
-    CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_lds = lds;
-  }
   const int nct = a.Cout / TC, npt = (a.M + TP - 1) / TP;
   b.rr_ks = ks;                                    // split-K on a small grid (planned: conv_plan.h splitk_ks)
   if (ks > 1 && !splitk_scratch(s, &b.sk_part, &b.sk_cnt)) return -10;
-  hipLaunchKernelGGL(kfn, dim3(nct * npt * b.rr_ks, nb), dim3(64 * WC * WP), lds, s, b);
-  return (int)hipGetLastError();
+  return launch_lds(conv_glds2_kernel<DT, WC, WP, PW, EPI>, attr_lds, dim3(nct * npt * b.rr_ks, nb), 64 * WC * WP, lds,
+                    s, b);
 }
 
 // ===========================================================================
@@ -1700,20 +1620,15 @@ __global__ void __launch_bounds__(512, 1) conv_rring_kernel(ConvArgs2 a) {
 
 template <int DT, int EPI, int TC, int TR, int LEAD, int D, bool RG>
 static int launch_rring_rg(const ConvArgs2& a, const ConvPlan& p, hipStream_t s) {
-  auto kfn = conv_rring_kernel<DT, EPI, D, LEAD, TC, TR, RG>;
-  static bool attr = false;
-  if (!attr) {
-    CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, rr_lds(TC, TR)));
-    attr = true;
-  }
+  static size_t attr_lds = 0;
   ConvArgs2 b = a;
   b.rr_tx = (a.W + 127) / 128;
   b.rr_ty = (a.H + TR - 1) / TR;
   b.rr_np = p.npt;
   b.rr_ks = p.ks;                             // (the pool epilogue too: same tiles, same split as conv_igemm)
   if (p.ks > 1 && !splitk_scratch(s, &b.sk_part, &b.sk_cnt)) return -10;
-  hipLaunchKernelGGL(kfn, dim3(p.tiles * p.ks), dim3(512), rr_lds(TC, TR), s, b);
-  return (int)hipGetLastError();
+  return launch_lds(conv_rring_kernel<DT, EPI, D, LEAD, TC, TR, RG>, attr_lds, dim3(p.tiles * p.ks), 512,
+                    rr_lds(TC, TR), s, b);
 }
 // the aligned (W % 128 == 0, H % TR == 0) or the ragged instantiation; rows are issued LEAD stages ahead of their
 // first tap (2-row tiles: 3, per layer 0.4 % ahead of 4, profiles/r3/ab_rring.txt)
@@ -1893,8 +1808,9 @@ conv_halo64_kernel(HaloConvArgs a) {
     flush_bias();
     return;
   }
+  constexpr bool BIASED = (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD);
   float bias[16];
-  if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD) {
+  if (BIASED) {   // (load_bias here reorders the bias epilogues' code; the 64 -> 128 forward measured 1 % slower)
 #pragma unroll
     for (int c = 0; c < 16; c += 4) {
       const float4 b4 = *reinterpret_cast<const float4*>(a.bias + chb + c);
@@ -1906,46 +1822,24 @@ conv_halo64_kernel(HaloConvArgs a) {
     const int ow = ow0 + colbase + i * 16 + fr;
     if (ow >= a.W) continue;
     float v[16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) v[j * 4 + q] = acc[j][i][q];
-    if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD) {
-      const bool cv = ow < a.wv;              // padding columns of a width-padded map stay zero
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        v[c] += bias[c];
-        if (EPI != EPI_BIAS) v[c] = fmaxf(v[c], 0.f);
-        v[c] = cv ? v[c] : 0.f;
-      }
-    }
+    frag_values(v, acc, i);
+    if (BIASED) bias_act<EPI, 16>(v, bias, ow < a.wv);   // padding columns of a width-padded map stay zero
     const size_t off = ((size_t)(n * a.H + oh) * a.W + ow) * CO + chb;
     if (EPI == EPI_MASK) {
       const uint4 m0 = *reinterpret_cast<const uint4*>(a.mask + off);
       const uint4 m1 = *reinterpret_cast<const uint4*>(a.mask + off + 8);
       const unsigned mw[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const unsigned short bits = (unsigned short)(mw[c >> 1] >> ((c & 1) * 16));
-        const bool pos = pos_bits(bits);
-        v[c] = pos ? v[c] : 0.f;
-        bs[c] += v[c];
-      }
+      relu_mask16<16, true>(v, mw, bs);
     }
-    const uint4 o0 =
-        make_uint4(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], v[3]), pack2<DT>(v[4], v[5]), pack2<DT>(v[6], v[7]));
-    const uint4 o1 =
-        make_uint4(pack2<DT>(v[8], v[9]), pack2<DT>(v[10], v[11]), pack2<DT>(v[12], v[13]), pack2<DT>(v[14], v[15]));
+    const uint4 o0 = pack8h<DT>(v), o1 = pack8h<DT>(v + 8);
     if (EPI != EPI_POOLFWD || a.y != nullptr) {
       *reinterpret_cast<uint4*>(a.y + off) = o0;
       *reinterpret_cast<uint4*>(a.y + off + 8) = o1;
     }
     if constexpr (EPI == EPI_BIAS_RELU) {
-      if (a.mbo != nullptr) {   // sign bits of the 16 channels this lane stored (EPI_MASKB layout)
-        const unsigned b = sign_bits8(o0.x, o0.y, o0.z, o0.w) | (sign_bits8(o1.x, o1.y, o1.z, o1.w) << 8);
+      if (a.mbo != nullptr)     // sign bits of the 16 channels this lane stored (EPI_MASKB layout)
         *reinterpret_cast<unsigned short*>(a.mbo + ((size_t)(n * a.H + oh) * a.W + ow) * (CO >> 3) + (chb >> 3)) =
-            (unsigned short)b;
-      }
+            (unsigned short)sign_bits16(o0, o1);
     }
     if constexpr (EPI == EPI_POOLFWD) {
       // staging tile [4 rows][64 cols] x 128 B, 16-B chunk c of column col at slot c ^ (col & 7)
@@ -1957,32 +1851,13 @@ conv_halo64_kernel(HaloConvArgs a) {
   }
   if constexpr (EPI == EPI_POOLFWD) {
     __syncthreads();
-    // 2 pooled rows x 32 pooled columns x 8 chunks of 8 channels: 512 outputs, 2 per thread; max of the
-    // stored (rounded) values, exactly what maxpool_fwd_kernel computes from the stored map
+    // 2 pooled rows x 32 pooled columns x 8 chunks of 8 channels: 512 outputs, 2 per thread
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int o = tid + 256 * u;
       const int c = o & 7, pc = (o >> 3) & 31, pr = o >> 8;
-      float m[8], t[4][8];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {     // q = window position in ATen order (row * 2 + column)
-        const int rr = 2 * pr + (q >> 1), cc = 2 * pc + (q & 1);
-        const uint4 v4 = reinterpret_cast<const uint4*>(halo + (rr * 64 + cc) * 128)[c ^ (cc & 7)];
-        unpack8h<DT>(v4, t[q]);
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) m[k] = fmaxf(fmaxf(t[0][k], t[1][k]), fmaxf(t[2][k], t[3][k]));
       const size_t pp = (size_t)(n * (a.H >> 1) + (oh0 >> 1) + pr) * (a.W >> 1) + (ow0 >> 1) + pc;
-      *reinterpret_cast<uint4*>(a.yp + pp * 64 + c * 8) = pack8h<DT>(m);
-      if (a.codes != nullptr) {
-        uint32_t cw = 0u;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const uint32_t first = (t[0][k] == m[k]) ? 1u : (t[1][k] == m[k]) ? 2u : (t[2][k] == m[k]) ? 4u : 8u;
-          cw |= ((m[k] > 0.f) ? first : 0u) << (4 * k);
-        }
-        a.codes[pp * 8 + c] = cw;
-      }
+      pool_staged_store<DT>(halo, pr, pc, c, pp, a.yp, a.codes);
     }
   }
   flush_bias();
@@ -2091,13 +1966,9 @@ __global__ void __launch_bounds__(512, 1) conv_ws64_kernel(HaloConvArgs a) {
     for (int ks = 0; ks < 18; ++ks)
       wf[ks][j] = __builtin_bit_cast(frag8_t, *reinterpret_cast<const uint4*>(wr + (ks >> 1) * 64 + (ks & 1) * 32));
   }
+  constexpr bool BIASED = (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD);
   float bias[8];
-  if constexpr (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD) {
-    const float4 b0 = *reinterpret_cast<const float4*>(a.bias + chb);
-    const float4 b1 = *reinterpret_cast<const float4*>(a.bias + chb + 4);
-    bias[0] = b0.x; bias[1] = b0.y; bias[2] = b0.z; bias[3] = b0.w;
-    bias[4] = b1.x; bias[5] = b1.y; bias[6] = b1.z; bias[7] = b1.w;
-  }
+  if constexpr (BIASED) load_bias<8>(bias, a.bias + chb);
   // per-lane halo offsets (swizzle keyed by the halo column: (fr + kw) & 7 for every fragment)
   int hoff[3][2];
 #pragma unroll
@@ -2188,12 +2059,14 @@ __global__ void __launch_bounds__(512, 1) conv_ws64_kernel(HaloConvArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int col = i * 16 + fr, ow = ow0 + col;
+      // (this kernel sits at its VGPR cap: with frag_values, bias_act, relu_mask16 / relu_mask_bits or pool_staged_store
+      // every instantiation compiles to other code, and the fused-pool forward measured 1 % slower)
       float v[8];
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[j * 4 + q] = acc[j][i][q];
-      if constexpr (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS || EPI == EPI_POOLFWD) {
+      if constexpr (BIASED) {
         const bool cv = ow < a.wv;            // padding columns of a width-padded map stay zero
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -2227,28 +2100,18 @@ __global__ void __launch_bounds__(512, 1) conv_ws64_kernel(HaloConvArgs a) {
     }
     if constexpr (EPI == EPI_POOLFWD) {
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      // 2 pooled rows x 32 pooled columns x 8 chunks of 8 channels = 512 outputs, one per thread; max of the
-      // stored (rounded) values and the first-max codes, exactly as maxpool_fwd_kernel from the stored map
+      // 2 pooled rows x 32 pooled columns x 8 chunks of 8 channels = 512 outputs, one per thread
       const int c = tid & 7, pc = (tid >> 3) & 31, pr = tid >> 8;
+      const size_t pp = (size_t)(n * (a.H >> 1) + (oh0 >> 1) + pr) * (a.W >> 1) + (ow0 >> 1) + pc;
       float m[8], tv[4][8];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {     // q = window position in ATen order (row * 2 + column)
         const int rr = 2 * pr + (q >> 1), cc = 2 * pc + (q & 1);
         unpack8h<DT>(reinterpret_cast<const uint4*>(cur + (rr * 64 + cc) * 128)[c ^ (cc & 7)], tv[q]);
       }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) m[k] = fmaxf(fmaxf(tv[0][k], tv[1][k]), fmaxf(tv[2][k], tv[3][k]));
-      const size_t pp = (size_t)(n * (a.H >> 1) + (oh0 >> 1) + pr) * (a.W >> 1) + (ow0 >> 1) + pc;
+      pool_max(tv, m);
       *reinterpret_cast<uint4*>(a.yp + pp * 64 + c * 8) = pack8h<DT>(m);
-      if (a.codes != nullptr) {
-        uint32_t cw = 0u;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const uint32_t first = (tv[0][k] == m[k]) ? 1u : (tv[1][k] == m[k]) ? 2u : (tv[2][k] == m[k]) ? 4u : 8u;
-          cw |= ((m[k] > 0.f) ? first : 0u) << (4 * k);
-        }
-        a.codes[pp * 8 + c] = cw;
-      }
+      if (a.codes != nullptr) a.codes[pp * 8 + c] = pool_codes(tv, m);
       // staging reads done before the next-but-one halo DMA overwrites `cur`
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
@@ -2337,15 +2200,9 @@ template <int DT, int EPI, bool W1G = false, bool MB = false>
 static int launch_ws64(const HaloConvArgs& a, hipStream_t s) {
   // 2 halo buffers of 6 rows x 72 pixel slots (+ W1G: 12 shifted image planes of 6 x 72 16-bit words)
   constexpr size_t lds = 2 * (size_t)(6 * 9) * 1024 + (W1G ? 12 * 6 * 72 * 2 + 13 * 256 + 8 * 192 * 16 : 0);
-  auto kfn = conv_ws64_kernel<DT, EPI, W1G, MB>;
-  static bool attr = false;
-  if (!attr) {
-    CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
+  static size_t attr_lds = 0;
   const int grid = ws64_grid(a.N * a.tiles_y * a.tiles_x, can_device_cus());   // every block gets a non-empty run
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, s, a);
-  return (int)hipGetLastError();
+  return launch_lds(conv_ws64_kernel<DT, EPI, W1G, MB>, attr_lds, dim3(grid), 512, lds, s, a);
 }
 
 // ===========================================================================
@@ -2406,11 +2263,8 @@ __global__ void __launch_bounds__(512, 4) conv_first_halo_kernel(HaloConvArgs a)
       af[kk][j] = __builtin_bit_cast(frag8_t, *reinterpret_cast<const uint4*>(a.w + perm_row_st64(j * 16 + fr) * 64 + kk * 32 + fq * 8));
   const int chb = fq * 8;                              // channel of v[0]; v[8] at chb + 32
   float bias[16];
-#pragma unroll
-  for (int c = 0; c < 16; c += 4) {
-    const float4 b4 = *reinterpret_cast<const float4*>(a.bias + chb + (c < 8 ? c : 24 + c));
-    bias[c] = b4.x; bias[c + 1] = b4.y; bias[c + 2] = b4.z; bias[c + 3] = b4.w;
-  }
+  load_bias<8>(bias, a.bias + chb);
+  load_bias<8>(bias + 8, a.bias + chb + 32);
   const int r = wave >> 1, colbase = (wave & 1) * 64;
 
   int t = PF ? (int)blockIdx.x : xcd_remap(blockIdx.x, ntile);
@@ -2452,16 +2306,12 @@ __global__ void __launch_bounds__(512, 4) conv_first_halo_kernel(HaloConvArgs a)
       const bool cv = ow < a.wv;              // padding columns of a width-padded map stay zero
       if constexpr (LS) {
         float v[16];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[j * 4 + q] = cv ? fmaxf(acc[j][q] + bias[j * 4 + q], 0.f) : 0.f;
+        frag_values(v, acc);
+        bias_act<EPI_BIAS_RELU, 16>(v, bias, cv);
         // pixel fr's 16-B chunks fq (channels 8fq..) and 4 + fq (32 + 8fq..) at slot chunk ^ (fr & 7)
         uint4* st = stg[wave];
-        st[fr * 8 + (fq ^ (fr & 7))] =
-            make_uint4(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], v[3]), pack2<DT>(v[4], v[5]), pack2<DT>(v[6], v[7]));
-        st[fr * 8 + ((4 + fq) ^ (fr & 7))] =
-            make_uint4(pack2<DT>(v[8], v[9]), pack2<DT>(v[10], v[11]), pack2<DT>(v[12], v[13]), pack2<DT>(v[14], v[15]));
+        st[fr * 8 + (fq ^ (fr & 7))] = pack8h<DT>(v);
+        st[fr * 8 + ((4 + fq) ^ (fr & 7))] = pack8h<DT>(v + 8);
         // read back pixel-major (wave-private tile: the wave's LDS ops retire in order)
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
@@ -2479,15 +2329,10 @@ __global__ void __launch_bounds__(512, 4) conv_first_halo_kernel(HaloConvArgs a)
       }
       if (oh >= a.H || ow >= a.W) continue;
       float v[16];
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[j * 4 + q] = cv ? fmaxf(acc[j][q] + bias[j * 4 + q], 0.f) : 0.f;
+      frag_values(v, acc);
+      bias_act<EPI_BIAS_RELU, 16>(v, bias, cv);
       const size_t off = ((size_t)(n * a.H + oh) * a.W + ow) * 64 + chb;
-      const uint4 q0 =
-          make_uint4(pack2<DT>(v[0], v[1]), pack2<DT>(v[2], v[3]), pack2<DT>(v[4], v[5]), pack2<DT>(v[6], v[7]));
-      const uint4 q1 =
-          make_uint4(pack2<DT>(v[8], v[9]), pack2<DT>(v[10], v[11]), pack2<DT>(v[12], v[13]), pack2<DT>(v[14], v[15]));
+      const uint4 q0 = pack8h<DT>(v), q1 = pack8h<DT>(v + 8);
       *reinterpret_cast<uint4*>(a.y + off) = q0;
       *reinterpret_cast<uint4*>(a.y + off + 32) = q1;
       if (a.mbo != nullptr) {   // sign bits of chunks fq (channels 8fq ..) and 4 + fq (32 + 8fq ..)
@@ -2506,30 +2351,18 @@ template <int DT, int CO, int EPI, int TCOL>
 static int launch_halo64(const HaloConvArgs& a, hipStream_t s) {
   constexpr int HALO_BYTES = ((6 * (TCOL + 2) + 7) / 8) * 1024;
   constexpr int NW = (CO == 64 && TCOL == 64) ? 4 : 8;
-  const size_t lds = HALO_BYTES + 3 * (size_t)CO * 128;
-  auto kfn = conv_halo64_kernel<DT, CO, EPI, TCOL>;
-  static bool attr = false;
-  if (!attr) {
-    CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  hipLaunchKernelGGL(kfn, dim3(a.N * a.tiles_y * a.tiles_x), dim3(64 * NW), lds, s, a);
-  return (int)hipGetLastError();
+  static size_t attr_lds = 0;
+  return launch_lds(conv_halo64_kernel<DT, CO, EPI, TCOL>, attr_lds, dim3(a.N * a.tiles_y * a.tiles_x), 64 * NW,
+                    HALO_BYTES + 3 * (size_t)CO * 128, s, a);
 }
 
 template <int DT, int WC, int WP, int PW, int EPI>
 static int launch_glds(const ConvArgs2& a, hipStream_t s) {
   constexpr int TC = 64 * WC, TP = 64 * PW * WP;
-  const size_t lds = 2 * (size_t)(TC + TP) * 128;
-  auto kfn = conv_glds_kernel<DT, WC, WP, PW, EPI>;
-  static bool attr = false;
-  if (!attr) {
-    CAN_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
+  static size_t attr_lds = 0;
   const int nct = a.Cout / TC, npt = (a.M + TP - 1) / TP;
-  hipLaunchKernelGGL(kfn, dim3(nct * npt), dim3(64 * WC * WP), lds, s, a);
-  return (int)hipGetLastError();
+  return launch_lds(conv_glds_kernel<DT, WC, WP, PW, EPI>, attr_lds, dim3(nct * npt), 64 * WC * WP,
+                    2 * (size_t)(TC + TP) * 128, s, a);
 }
 
 // The LDS-DMA / row-ring launch of a plan: config -> template arguments (the WC, WP, PW / TC, TR of kTileCfgs), for

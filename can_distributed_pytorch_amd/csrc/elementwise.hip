@@ -15,6 +15,7 @@
 //                       device-side non-finite flag             train.py:126
 //   img_to_nhwc4        [N,3,H,W] fp32 -> [N,H,W,4] bf16 (first-layer input)
 #include "common.h"
+#include "conv_epilogue.h"
 
 namespace can {
 
@@ -37,18 +38,9 @@ __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const uint4* __restric
     unpack8h<DT>(x[base + C8], t[1]);
     unpack8h<DT>(x[base + (size_t)W * C8], t[2]);
     unpack8h<DT>(x[base + (size_t)W * C8 + C8], t[3]);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) m[k] = fmaxf(fmaxf(t[0][k], t[1][k]), fmaxf(t[2][k], t[3][k]));
+    pool_max(t, m);
     y[i] = pack8h<DT>(m);  // exact: max of bf16 values is a bf16 value
-    if (codes != nullptr) {
-      uint32_t cw = 0u;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const uint32_t first = (t[0][k] == m[k]) ? 1u : (t[1][k] == m[k]) ? 2u : (t[2][k] == m[k]) ? 4u : 8u;
-        cw |= ((m[k] > 0.f) ? first : 0u) << (4 * k);
-      }
-      codes[i] = cw;
-    }
+    if (codes != nullptr) codes[i] = pool_codes(t, m);
   }
 }
 
