@@ -95,6 +95,8 @@ int can_ctx_fuse(const void* fv, const void* ws, const float* T, void* cat, int 
                  void* stream);
 int can_ctx_bwd_e1(const void* dcat, const void* ws, const float* T, void* dz, void* sdir, int N, int h, int w, int C,
                    int dt, void* stream);
+// 1: matrix-core kernel, 0: tiled kernel, < 0: refused (the choice can_ctx_gemm makes; host only)
+int can_ctx_gemm_form(int N, int C);
 int can_ctx_gemm(int mode, const float* x, const float* y, const float* const* w, float* out, float* const* gw, int N,
                  int C, float beta, float scale, const float* dscale, void* stream);
 // linearised context module (conv_igemm.hip EPI_CTXF / EPI_CTXB + context.hip ctx_bwd_lin)

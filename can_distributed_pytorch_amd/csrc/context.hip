@@ -1023,12 +1023,21 @@ extern "C" int can_ctx_bwd_final(const void* dcat, const void* dc, const float* 
   return (int)hipGetLastError();
 }
 
+// Which kernel can_ctx_gemm launches for a batch of N images at C channels: 1 the matrix-core form (ctx_mm_kernel,
+// K <= 512 on both sides: C channels and the N * 36 cell rows of scale 6), 0 the tiled form (ctx_gemm_kernel), -2 a
+// shape it refuses.  Host code only; can_ctx_gemm decides by it, so the rule exists once.
+extern "C" int can_ctx_gemm_form(int N, int C) {
+  if (C < 64 || C % 64 != 0 || N < 1) return -2;   // 16-B rows, 64-column tiles
+  return (C <= 512 && N * 36 <= 512) ? 1 : 0;
+}
+
 // conv{S}_1 GEMMs of all four scales in one launch.  mode 0: out = table (fwd), mode 1: out = dave,
 // mode 2: gw = dW1 per scale (beta: accumulate, scale/dscale: gradient scaling of the fp16 step).
 extern "C" int can_ctx_gemm(int mode, const float* x, const float* y, const float* const* w, float* out,
                             float* const* gw, int N, int C, float beta, float scale, const float* dscale,
                             void* stream) {
-  if (C % 64 != 0 || N < 1) return -2;   // 16-B rows, 64-column tiles
+  const int form = can_ctx_gemm_form(N, C);
+  if (form < 0) return form;
   CtxGemmArgs a{};
   a.x = x; a.y = y; a.out = out; a.N = N; a.C = C; a.beta = beta; a.scale = scale; a.dscale = dscale;
   for (int i = 0; i < 4; ++i) {
@@ -1037,7 +1046,7 @@ extern "C" int can_ctx_gemm(int mode, const float* x, const float* y, const floa
   }
   const int M = (mode == 2) ? C : N * 36;
   hipStream_t s = (hipStream_t)stream;
-  if (C <= 512 && N * 36 <= 512) {
+  if (form == 1) {
     // matrix-core form (K <= 512 on both sides): 16 x 16 tiles, K split over 8 waves
     const dim3 grid(C / 16, (M + 15) / 16, 4);
     if (mode == 0) hipLaunchKernelGGL(ctx_mm_kernel<0>, grid, dim3(512), 0, s, a);

@@ -139,6 +139,27 @@ def conv1x1_cells(cells, W):
     return torch.cat([_grid(t, si).reshape(t.shape[0], -1, t.shape[2]) @ Wd[si].t() for si in range(4)], 1)
 
 
+def conv1x1_cells_t(cells, W):
+    """The transposed 1x1 conv (its data gradient): cells [N, 50, C_out], W [4, C_out, C_in] -> [N, 50, C_in]."""
+    t, Wd = cells.to(F64), W.to(F64)
+    return torch.cat([_grid(t, si).reshape(t.shape[0], -1, t.shape[2]) @ Wd[si] for si in range(4)], 1)
+
+
+def wgrad_cells(d, x):
+    """The 1x1 convs' weight gradients over the cells: d [N, 50, C_out], x [N, 50, C_in] -> [4, C_out, C_in],
+    dW_S = sum over the N S^2 cells of scale S of d[cell] x[cell]^T."""
+    dd, xd = d.to(F64), x.to(F64)
+    return torch.stack([torch.einsum("nrc,nrk->ck", dd[:, o:o + S * S], xd[:, o:o + S * S])
+                        for S, o in zip(SCALES, CELL_OFF)])
+
+
+def wgrad_maps(d, x):
+    """The 1x1 convs' weight gradients over maps: d [4, N, h, w, C_out], x [4, N, h, w, C_in] or [N, h, w, C_in] (one
+    input for the four scales) -> [4, C_out, C_in]."""
+    dd, xd = d.to(F64), x.to(F64)
+    return torch.einsum("snyxc,snyxk->sck" if xd.dim() == 5 else "snyxc,nyxk->sck", dd, xd)
+
+
 def conv1x1_maps(maps, W):
     """maps [4, N, h, w, C_in], W [4, C_out, C_in] -> [4, N, h, w, C_out] (scale S's conv on scale S's map)."""
     return torch.einsum("snyxk,sck->snyxc", maps.to(F64), W.to(F64))
@@ -240,6 +261,86 @@ def context_backward(fv, dcat, W1, W2, geo, linear=True):
     dc = conv1x1_maps(dz, W2t)
     dA = upsample_adjoint(sdir + dc, geo)
     return dfv_direct(dc, dcat_fv, conv1x1_cells(dA, W1t), fv, geo)
+
+
+# --------------------------------------------------------------------------------------------------- weight gradients
+# (n, h, w) of the weight-gradient stages (a subset of the shapes above; PADDED_SHAPE joins the linear ones) and their
+# (beta, scale, dscale) settings: a fresh gradient, the accumulation window, the fp16 step's loss scale on top of it.
+# In the third, scale * dscale = 1: a term that misses the whole factor cannot be told there, hence the fourth (1 / 8)
+WGRAD_LINEAR_SHAPES = [(3, 5, 65), (2, 13, 96)]
+WGRAD_DIRECT_SHAPES = [(3, 2, 3), (2, 13, 17)]
+WGRAD_SETTINGS = [(0.0, 1.0, None), (1.0, 1.0, None), (1.0, 2.0, 0.5), (1.0, 0.25, 0.5)]
+
+# Mistakes a schedule can make (tests/test_ctx_reference_cpu.py proves that the stage check sees each of them) -> the
+# gradients that own it, per form
+WGRAD_MISTAKES = {
+    "drop_dtu": dict(linear=("dW2",)),                     # the dt^T u term of dW2 left out
+    "flip_dtu": dict(linear=("dW2",)),                     # ... or subtracted
+    "scatter_rows": dict(linear=("dW2",)),                 # dW2cat's rows read as si * C + c instead of 4c + si
+    "beta_twice": dict(linear=("dW2",)),                   # beta applied by the scatter AND the second term: 2 beta g0
+    "scale_one_term": dict(linear=("dW2",)),               # scale * dscale on dG^T fv only
+    "no_dscale": dict(linear=("dW1", "dW2"), direct=("dW1", "dW2")),
+    "cells_swapped": dict(linear=("dW1", "dW2"), direct=("dW1",)),       # ave / u of scales 3 and 6 read transposed
+    "cells_next_image": dict(linear=("dW1", "dW2"), direct=("dW1",)),    # ave / u taken from the next image
+}
+
+
+def wgrad_mistake_live(name, form, n, beta, scale, dscale):
+    """Whether the mistake can be made at all in this case (and would change a gradient)."""
+    if form not in WGRAD_MISTAKES[name]:
+        return False
+    if name == "beta_twice":
+        return beta != 0.0
+    if name == "scale_one_term":
+        return scale * (1.0 if dscale is None else dscale) != 1.0
+    if name == "no_dscale":
+        return dscale is not None and dscale != 1.0
+    if name == "cells_next_image":
+        return n >= 2
+    return True
+
+
+def swap_cells(cells):
+    """i and j swapped inside the cells of scales 3 and 6."""
+    grids = cells_to_grids(cells)
+    return grids_to_cells(grids[:2] + [g.transpose(2, 3) for g in grids[2:]])
+
+
+def wgrad_stage(form, k, g0, beta, scale, dscale, mistake=None):
+    """What the context backward leaves in the conv{S}_1 / conv{S}_2 gradient buffers, in fp64 -> (dW1, dW2), each
+    [4, C, C]: beta g0 + scale dscale (fresh), from the kernels' own operands ``k``:
+      linear form  dW1_S = du_all_S^T ave_S, dW2_S = dG_S^T fv + dt_S^T u_S   (dg [4, N, h, w, C] the stored 16-bit dG;
+                   dt, u, du_all, ave the fp32 cell tables, du_all = du + W2^T dt)
+      direct form  dW1_S = dA_S^T ave_S,     dW2_S = dz_S^T cs_S              (dz, cs [4, N, h, w, C]).
+    g0 = (old dW1, old dW2), not read at beta = 0; dscale: a float or None.  mistake: a key of WGRAD_MISTAKES."""
+    assert mistake is None or form in WGRAD_MISTAKES[mistake], (mistake, form)
+    sd = scale * (1.0 if dscale is None or mistake == "no_dscale" else dscale)
+
+    def cells(t):
+        if mistake == "cells_swapped":
+            return swap_cells(t)
+        return t.roll(-1, 0) if mistake == "cells_next_image" else t
+    ave = cells(k["ave"])
+    if form == "linear":
+        f1 = sd * wgrad_cells(k["du_all"], ave)
+        a = wgrad_maps(k["dg"], k["fv"])
+        if mistake == "scatter_rows":
+            c = a.shape[1]
+            a = a.permute(1, 0, 2).reshape(4 * c, c).reshape(4, c, c)     # dW2cat (rows 4c + si) read as [si][c]
+        b = wgrad_cells(k["dt"], cells(k["u"]))
+        b = {"drop_dtu": 0.0, "flip_dtu": -1.0}.get(mistake, 1.0) * b
+        f2 = sd * a + (1.0 if mistake == "scale_one_term" else sd) * b
+    else:
+        f1 = sd * wgrad_cells(k["dA"], ave)
+        f2 = sd * wgrad_maps(k["dz"], k["cs"])
+    if beta == 0.0:
+        return f1, f2
+    return beta * g0[0].to(F64) + f1, (2.0 if mistake == "beta_twice" else 1.0) * beta * g0[1].to(F64) + f2
+
+
+def wgrad_sum32_ratio(got, ref):
+    """sum32_ratio of a stack of the four scales' weight gradients [4, C, C], scale by scale."""
+    return max(sum32_ratio(got[si], ref[si]) for si in range(4))
 
 
 # ------------------------------------------------------------------------------------------------------------- inputs

@@ -7,7 +7,9 @@
 * the sensitivity of the stage checks of tests/test_gpu_context_stages.py: on the structured inputs and at the shapes
   of that test, the clean reference rounded to bf16 / fp16 passes every stage check with zero outliers, and every
   deliberate mistake in the reference's OWN geometry fails the check of the stage that owns it, forward and adjoint
-  (the pattern of tests/test_numerics_checker.py).  No project code is perturbed and nothing here runs on a GPU.
+  (the pattern of tests/test_numerics_checker.py).  No project code is perturbed and nothing here runs on a GPU;
+* the cell GEMM references (forward, transpose, weight gradient over cells) against fp64 matmuls and autograd, and the
+  sensitivity of the dW1 / dW2 stage checks to every mistake of ctx_reference.WGRAD_MISTAKES.
 """
 import types
 
@@ -253,6 +255,100 @@ def test_stage_checks_pass_clean_and_catch_every_mutation(n, h, w, dtype):
             assert r["c"] > 1.0 and r["fi"] > 1.0, (mut.__name__, "upsampling stage, forward", r)
             assert r["dt"] > 1.0 and r["du"] > 1.0, (mut.__name__, "upsampling stage, adjoint", r)
     assert live >= 3, live
+
+
+# ------------------------------------------------------------------------------------- cell GEMMs and weight gradients
+@pytest.mark.parametrize("n,c", [(1, 8), (3, 16)])
+def test_cell_gemms_vs_torch_fp64(n, c):
+    """conv1x1_cells, its transpose and the per-scale weight gradient over cells (the three modes of the kernels'
+    ctx_gemm) against plain fp64 matmuls on the [N, 50, C] layout, scale by scale; wgrad_maps against autograd."""
+    g = torch.Generator().manual_seed(21 + n)
+    x = torch.randn(n, 50, c, generator=g, dtype=F64)
+    d = torch.randn(n, 50, c, generator=g, dtype=F64)
+    W = torch.randn(4, c, c, generator=g, dtype=F64)
+    fwd, bwd, dw = R.conv1x1_cells(x, W), R.conv1x1_cells_t(d, W), R.wgrad_cells(d, x)
+    assert fwd.shape == bwd.shape == (n, 50, c) and dw.shape == (4, c, c)
+    for si, (S, o) in enumerate(zip(SCALES, R.CELL_OFF)):
+        rows_x, rows_d = x[:, o:o + S * S].reshape(-1, c), d[:, o:o + S * S].reshape(-1, c)
+        _close(fwd[:, o:o + S * S].reshape(-1, c), rows_x @ W[si].t(), ("forward", S))
+        _close(bwd[:, o:o + S * S].reshape(-1, c), rows_d @ W[si], ("transpose", S))
+        _close(dw[si], rows_d.t() @ rows_x, ("weight gradient", S))
+    # and as gradients of <d, conv1x1_cells(x, W)> by autograd
+    xl, Wl = x.clone().requires_grad_(True), W.clone().requires_grad_(True)
+    gx, gW = torch.autograd.grad((R.conv1x1_cells(xl, Wl) * d).sum(), [xl, Wl])
+    _close(bwd, gx, "transpose, autograd")
+    _close(dw, gW, "weight gradient, autograd")
+    maps = torch.randn(4, n, 3, 5, c, generator=g, dtype=F64)
+    dm = torch.randn(4, n, 3, 5, c, generator=g, dtype=F64)
+    Wm = W.clone().requires_grad_(True)
+    (gm,) = torch.autograd.grad((R.conv1x1_maps(maps, Wm) * dm).sum(), [Wm])
+    _close(R.wgrad_maps(dm, maps), gm, "wgrad_maps")
+    (g1,) = torch.autograd.grad((R.conv1x1_maps(maps[0][None].expand(4, -1, -1, -1, -1), Wm) * dm).sum(), [Wm])
+    _close(R.wgrad_maps(dm, maps[0]), g1, "wgrad_maps, one input")
+
+
+def _wgrad_operands(form, n, h, w, dtype, std=W_STD):
+    """The operands of the weight-gradient stages as correct kernels would hold them (16-bit maps, fp32 cells), from
+    the clean reference at C_CPU channels."""
+    geo = R.Geometry(h, w)
+    W1, W2 = _weights(C_CPU, 11, std)
+    W2 = W2.to(dtype).to(F64)
+    fv = R.structured_fv(n, h, w, C_CPU, dtype, seed=100 * h + w)
+    g = torch.Generator().manual_seed(7)
+    dfi = torch.randn(n, h, w, 2 * C_CPU, generator=g).to(dtype)[..., C_CPU:]
+    ave = R.pool_cells(fv, geo).float()
+    u = R.conv1x1_cells(ave, W1).float()
+    s = R.upsample(u, geo)
+    if form == "linear":
+        wts = R.weights_and_fi(fv, u, R.conv1x1_cells(u, W2), W2, geo)[0].to(dtype)
+        dz, ds = R.bwd_pointwise(dfi, wts, s)
+        dt = R.upsample_adjoint(dz, geo).float()
+        du_all = (R.upsample_adjoint(ds, geo) + R.conv1x1_cells_t(dt, W2)).float()
+        return dict(fv=fv, dg=(-dz).to(dtype), dt=dt, u=u, du_all=du_all, ave=ave)
+    cs = R.direct_c(u, fv, geo).to(dtype)
+    wts = torch.sigmoid(R.conv1x1_maps(cs, W2)).to(dtype)
+    dz, sdir = R.bwd_pointwise(dfi, wts, s)
+    dz = dz.to(dtype)
+    dc = R.conv1x1_maps(dz, W2.transpose(1, 2)).to(dtype)
+    dA = R.upsample_adjoint(sdir.to(dtype).to(F64) + dc.to(F64), geo).float()
+    return dict(dz=dz, cs=cs, dA=dA, ave=ave)
+
+
+WGRAD_CASES = [("linear",) + s for s in R.WGRAD_LINEAR_SHAPES + [R.PADDED_SHAPE]] + \
+              [("direct",) + s for s in R.WGRAD_DIRECT_SHAPES]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("form,n,h,w", WGRAD_CASES)
+def test_wgrad_stage_checks_pass_clean_and_catch_every_mistake(form, n, h, w, dtype):
+    """The dW1 / dW2 stage checks of tests/test_gpu_context_stages.py (check_sum32 at its default 1e-3, scale by
+    scale) on the CPU, at the same shapes and (beta, scale, dscale) settings with C_CPU channels: the reference
+    rounded to fp32 passes, and every mistake of ctx_reference.WGRAD_MISTAKES pushes at least one scale of every
+    gradient that owns it over the bound, wherever it can be made.  The conv{S}_1 / conv{S}_2 std is the module
+    tests' 0.05 (W_STD at C_CPU channels): dt^T u is large enough to be seen at it, so it is not raised."""
+    k = _wgrad_operands(form, n, h, w, dtype)
+    gen = torch.Generator().manual_seed(13)
+    seen = set()
+    for beta, scale, dscale in R.WGRAD_SETTINGS:
+        fresh = R.wgrad_stage(form, k, None, 0.0, 1.0, None)
+        # old contents at the rms of the fresh gradient, as the GPU test draws them
+        g0 = tuple(torch.randn(f.shape, generator=gen) * f.pow(2).mean((1, 2), keepdim=True).sqrt().float()
+                   for f in fresh)
+        ref = dict(zip(("dW1", "dW2"), R.wgrad_stage(form, k, g0, beta, scale, dscale)))
+        for name, r in ref.items():
+            assert R.wgrad_sum32_ratio(r.float(), r) <= 1.0, (name, "clean")
+        for mistake, owners in R.WGRAD_MISTAKES.items():
+            if not R.wgrad_mistake_live(mistake, form, n, beta, scale, dscale):
+                continue
+            seen.add(mistake)
+            bad = dict(zip(("dW1", "dW2"), R.wgrad_stage(form, k, g0, beta, scale, dscale, mistake)))
+            for name in ("dW1", "dW2"):
+                ratio = R.wgrad_sum32_ratio(ref[name].float(), bad[name])
+                if name in owners[form]:
+                    assert ratio > 1.0, (mistake, name, (beta, scale, dscale), ratio)
+                else:
+                    assert ratio <= 1.0, (mistake, name, "a gradient the mistake does not touch", ratio)
+    assert seen == {m for m, o in R.WGRAD_MISTAKES.items() if form in o}, seen
 
 
 def test_every_mutation_is_live_at_some_shape():

@@ -11,7 +11,12 @@ Storage points the reference follows (read off the kernels):
     16-bit pack; fi is formed from the fp32 sigmoid values, so its reference uses the reference's own w;
   * direct form (context.hip ctx_fuse / ctx_bwd_e1): fi, dz and sdir are formed from the stored 16-bit w, so their
     reference reads the kernel's w;
-  * both backwards (ctx_bwd_lin, ctx_bwd_e1) read the stored 16-bit w and recompute s and fi from the cell table.
+  * both backwards (ctx_bwd_lin, ctx_bwd_e1) read the stored 16-bit w and recompute s and fi from the cell table;
+  * the eight weight gradients (stages dW1 / dW2) come from the executor's own _context_bwd, so the schedule is under
+    test too: linear form dW1_S = du_all_S^T ave_S and dW2_S = dG_S^T fv + dt_S^T u_S from the stored 16-bit dG and
+    the fp32 cell tables, direct form dW1_S = dA_S^T ave_S and dW2_S = dz_S^T cs_S, each beta g0 + scale dscale (...)
+    at the settings of ctx_reference.WGRAD_SETTINGS.  tests/test_ctx_reference_cpu.py proves that the check sees a
+    dropped, flipped, misplaced, doubly accumulated or wrongly scaled term and misread cell tables.
 """
 import types
 
@@ -88,6 +93,16 @@ class Checks:
             detail = str(e)
         self._note(stage, max(R.cells_sum32_ratio(got, ref), 2.0 if detail else 0.0), detail)
 
+    def wgrad32(self, stage, got, ref):
+        """The four scales' weight gradients [4, C, C]: check_sum32 at its default tolerance, scale by scale."""
+        detail = ""
+        try:
+            for si, S in enumerate(SCALES):
+                check_sum32(got[si], ref[si].float(), what=f"{stage}, scale {S}")
+        except AssertionError as e:
+            detail = str(e)
+        self._note(stage, max(R.wgrad_sum32_ratio(got, ref), 2.0 if detail else 0.0), detail)
+
     def pool(self, stage, got, fv, geo):
         self._note(stage, R.pool_ratio(got, fv, geo))
 
@@ -136,8 +151,8 @@ def _kernels_linear(cx, fv, dcat, dave_r, wv=None):
     dcat0[..., :c] = 0
     dfv_pool = CV.conv_ctx_bwd(torch.zeros_like(dg), ex.ctx2cat_dgr, dave_r, dcat0, fv, wvalid=wv)
     torch.cuda.synchronize()
-    return dict(ave=sv["ave"], u=u, t=t, wts=sv["wts"], cat=cat, dg=dg, dt=dt, du=du, dave=dave, dfv=dfv,
-                dfv_pool=dfv_pool)
+    return dict(ave=sv["ave"], u=u, t=t, wts=sv["wts"], cat=cat, dg=dg, dt=dt, du=du, du_all=du_all, dave=dave,
+                dfv=dfv, dfv_pool=dfv_pool, saved=sv)
 
 
 def _check_linear(cx, k, fv, dcat, dave_r):
@@ -223,7 +238,7 @@ def _kernels_direct(cx, fv, dcat, dave_r):
                        dfv_pool.data_ptr(), n, h, w, c, ex.dt, st)
     torch.cuda.synchronize()
     return dict(ave=sv["ave"], table=sv["table"], cs=sv["cs"], wts=sv["wts"], cat=cat, dz=dz, sdir=sdir, dc=dc, dA=dA,
-                dave=dave, dfv=dfv, dfv_pool=dfv_pool)
+                dave=dave, dfv=dfv, dfv_pool=dfv_pool, saved=sv)
 
 
 def _check_direct(cx, k, fv, dcat, dave_r):
@@ -301,6 +316,88 @@ def test_one_row_or_one_column_maps_are_refused(ctx, dispatch_cfg, n, h, w):
     with pytest.raises(RuntimeError, match="rc=-7"):
         ex._conv(last, torch.zeros(n, h, w, last.cin, dtype=ctx.dtype, device="cuda"))
     torch.cuda.synchronize()
+
+
+# ----------------------------------------------------------------------------------------------------- weight gradients
+WGRAD_IDS = ["fresh", "accumulate", "accumulate-loss-scale", "accumulate-scale-eighth"]
+
+
+def _wgrad_stages(cx, form, k, ops, fv, dcat, beta, scale, dscale):
+    """The dW1 / dW2 stages: the executor's own _context_bwd (side=None: every launch on the compute stream) writes
+    the eight conv{S}_1 / conv{S}_2 gradients into real buffers -- the dW2cat weight gradient, the scatter, the
+    beta = 1 second term and the cell GEMMs of mode 2 as the schedule chains them -- and each is compared with
+    ctx_reference.wgrad_stage of the kernels' own operands ``ops`` (teacher forcing: ``k`` holds the outputs of the
+    fixed-order kernels, which the backward re-runs bitwise).  fv, dcat: the maps the executor is run on (padded in the
+    padded case; ``ops`` then holds the valid columns).  The old contents are NaN at beta = 0 (not read) and random
+    at the rms of the fresh gradient otherwise."""
+    from can_distributed_pytorch_amd.ops import conv as CV
+    ex = cx.ex
+    arena = torch.full((8, C, C), float("nan"), dtype=torch.float32, device="cuda")
+    g0 = None
+    if beta != 0.0:
+        gen = torch.Generator().manual_seed(17)
+        fresh = R.wgrad_stage(form, ops, None, 0.0, 1.0, None)
+        g0 = tuple(torch.randn(4, C, C, generator=gen).cuda() * f.pow(2).mean((1, 2), keepdim=True).sqrt().float()
+                   for f in fresh)
+        arena[:4], arena[4:] = g0
+    grads = [None] * len(ex._params())
+    for si, s in enumerate(SCALES):
+        grads[ex.ctx1_index[s]] = arena[si].view(C, C, 1, 1)
+        grads[ex.ctx2_index[s]] = arena[4 + si].view(C, C, 1, 1)
+    dsc = None if dscale is None else torch.tensor([dscale], dtype=torch.float32, device="cuda")
+    done = []
+    ex._context_bwd(k["saved"], fv, dcat, grads, CV.WgradWorkspace(fv.device), beta, scale, done.extend, dsc, None)
+    torch.cuda.synchronize()
+    assert sorted(done) == sorted([ex.ctx1_index[s] for s in SCALES] + [ex.ctx2_index[s] for s in SCALES])
+    ref1, ref2 = R.wgrad_stage(form, ops, g0, beta, scale, dscale)
+    ck = Checks(cx, form)
+    ck.wgrad32("dW1", arena[:4], ref1)
+    ck.wgrad32("dW2", arena[4:], ref2)
+    ck.done()
+
+
+def _linear_ops(k, fv, w):
+    """The operands of the linear form's weight gradients at the valid columns."""
+    n, h = fv.shape[:2]
+    return dict(fv=fv[:, :, :w], dg=_scales_first(k["dg"][:, :, :w], n, h, w), dt=k["dt"], u=k["u"],
+                du_all=k["du_all"], ave=k["ave"])
+
+
+@pytest.mark.parametrize("beta,scale,dscale", R.WGRAD_SETTINGS, ids=WGRAD_IDS)
+@pytest.mark.parametrize("n,h,w", R.WGRAD_LINEAR_SHAPES)
+def test_linear_wgrad_stages(ctx, dispatch_cfg, n, h, w, beta, scale, dscale):
+    dispatch_cfg(ctx_linear=1)
+    fv, dcat, dave_r = _inputs(n, h, w, ctx.dtype, seed=1000 * h + w)
+    assert ctx.ex._ctx_linear(fv)
+    k = _kernels_linear(ctx, fv, dcat, dave_r)
+    _wgrad_stages(ctx, "linear", k, _linear_ops(k, fv, w), fv, dcat, beta, scale, dscale)
+
+
+@pytest.mark.parametrize("beta,scale,dscale", R.WGRAD_SETTINGS, ids=WGRAD_IDS)
+def test_linear_wgrad_stages_width_padded(ctx, dispatch_cfg, beta, scale, dscale):
+    """The 127-column map at a row pitch of 128: the weight gradients are those of the 127-column map (the padding
+    column of dG and fv is zero and adds nothing)."""
+    n, h, w = R.PADDED_SHAPE
+    pitch = 128
+    dispatch_cfg(ctx_linear=1)
+    fv, dcat, dave_r = _inputs(n, h, w, ctx.dtype, seed=1000 * h + w)
+    fvp = torch.zeros(n, h, pitch, C, dtype=ctx.dtype, device="cuda")
+    fvp[:, :, :w] = fv
+    dcatp = torch.zeros(n, h, pitch, 2 * C, dtype=ctx.dtype, device="cuda")
+    dcatp[:, :, :w] = dcat
+    k = _kernels_linear(ctx, fvp, dcatp, dave_r, wv=w)
+    assert k["saved"]["wv"] == w
+    _wgrad_stages(ctx, "linear", k, _linear_ops(k, fvp, w), fvp, dcatp, beta, scale, dscale)
+
+
+@pytest.mark.parametrize("beta,scale,dscale", R.WGRAD_SETTINGS, ids=WGRAD_IDS)
+@pytest.mark.parametrize("n,h,w", R.WGRAD_DIRECT_SHAPES)
+def test_direct_wgrad_stages(ctx, dispatch_cfg, n, h, w, beta, scale, dscale):
+    fv, dcat, dave_r = _inputs(n, h, w, ctx.dtype, seed=1000 * h + w)
+    assert not ctx.ex._ctx_linear(fv)
+    k = _kernels_direct(ctx, fv, dcat, dave_r)
+    ops = dict(dz=k["dz"], cs=k["cs"], dA=k["dA"], ave=k["ave"])
+    _wgrad_stages(ctx, "direct", k, ops, fv, dcat, beta, scale, dscale)
 
 
 # ------------------------------------------------------------------------------------------------------ batch isolation

@@ -488,6 +488,18 @@ def test_wgrad_beta_scale_dscale(n, h, w, ci, co, dil, beta, dscale_k, dtype, di
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n,h,w,beta,scale,dscale_k", [(1, 3, 64, 0.0, 1.0, None), (2, 5, 67, 0.0, 1.0, None),
+                                                       (2, 5, 67, 0.5, 0.25, 3)])
+def test_wgrad_ctx_dw2cat_shape(n, h, w, beta, scale, dscale_k, dtype, dispatch_cfg):
+    """The linearised context module's dW2cat launch (ops/context_exec.py ctx2_wgrad): 1x1, 512 -> 2048, no bias.
+    wgrad_plan.h gives it cfg 9 by the "1x1 with many output rows" rule (K = 512 < 2048): 8 x 2 tiles of 256 x 256,
+    at most 16 pixel slices of whole 64-pixel stages (3 slices at M = 192, 11 at M = 670), so wgrad_reduce2_kernel<1>
+    sums the slabs; the v2 kernel at a width of 64, the v1 kernel of cfg 7's tiles at 67 (asserted by _check_wgrad)."""
+    dispatch_cfg(wgrad_tap=0)
+    _check_wgrad(n, h, w, 512, 2048, 1, 1, dtype, 9, "r1", beta=beta, scale=scale, dscale_k=dscale_k, bias=False)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_wgrad_1x1_batched(dtype):
     C, _, _ = _mods()
     nb, n, h, w, c = 4, 2, 12, 128, 512

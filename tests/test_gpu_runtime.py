@@ -14,9 +14,10 @@ def _rel(a, b):
     return ((a.float() - b.float()).norm() / (b.float().norm() + 1e-12)).item()
 
 
-@pytest.mark.parametrize("n", [1, 3, 8])
+@pytest.mark.parametrize("n", [1, 3, 8, 15])
 def test_ctx_gemm_all_modes_vs_fp32(n):
-    """conv{S}_1 forward / data-gradient / weight-gradient of all four scales (one launch each) vs torch fp32."""
+    """conv{S}_1 forward / data-gradient / weight-gradient of all four scales (one launch each) vs torch fp32.
+    Batch 15 runs the tiled kernel, the others the matrix-core one (bit for bit: tests/test_gpu_ctx_gemm_exact.py)."""
     from can_distributed_pytorch_amd.ops import _ext
     C = _ext.require()
     c = 512
@@ -228,7 +229,7 @@ def _layer_local_errors(st, img, gt, rec):
     for dy, x, ksize, dil in rec["wgrad"]:
         s = ident.get(x.data_ptr())
         if s is None or ksize != 3:
-            continue                              # context 1x1 weight gradients: covered by the fp32 comparison
+            continue      # context 1x1 weight gradients: the dW1 / dW2 stages of tests/test_gpu_context_stages.py
         if s.idx == 1 and s in ex.front:
             conv12_dy = dy
         dw = torch.nn.grad.conv2d_weight(nchw(x)[:, :s.cin], (s.cout, s.cin, 3, 3), nchw(dy), padding=dil,
