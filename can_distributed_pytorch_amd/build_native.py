@@ -95,6 +95,9 @@ def _newer(src_files, target) -> bool:
 
 
 ASAN_HOST = ["-fsanitize=address", "-fno-omit-frame-pointer", "-g"]
+# flags of single translation units: the fp32 elementwise kernels of bayes.hip are compiled without the packed fp32
+# VALU forms (scalar v_add / v_mul / v_fma only), so every one of their roundings is the plain instruction's
+UNIT_FLAGS = {"bayes.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _compile(src: str, headers, verbose=False, asan: bool = False) -> str:
@@ -107,6 +110,7 @@ def _compile(src: str, headers, verbose=False, asan: bool = False) -> str:
     common += extra_flags()
     if src.endswith(".hip"):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-x", "hip", "-c", src, "-o", obj, "-munsafe-fp-atomics"] + common
+        cmd += UNIT_FLAGS.get(os.path.basename(src), [])
         if asan:   # host half only: each -fsanitize right after -Xarch_host
             cmd += [f for flag in ASAN_HOST for f in ("-Xarch_host", flag)]
     else:

@@ -121,6 +121,26 @@ int can_gt_from_heads(const float* heads, const long long* ranges, const long lo
                       long long n_heads, const long long* ranges_host, const long long* desc_host, int n, float* gt,
                       int CH, int CW, int ds, void* stream);
 
+// bayes.hip: the Bayesian point loss on head records (README, "Bayesian loss")
+// the points of n crop windows from a heads pack's table, all on the device: pts [T][2] fp32 crop pixels, sample s from
+// slot begins[s] on in table order, cnt [n] int32 the heads inside each window.  No check of its own: the pack has
+// passed can_gt_from_heads_check.
+int can_crop_points(const float* heads, const long long* ranges, const long long* desc, const long long* begins, int n,
+                    float* pts, int* cnt, int CH, int CW, int ds, void* stream);
+// normaliser, expectation and gradient passes: et [n][h][w] dense, begins [n + 1] int64 (begins[n] = T), max_count the
+// largest begins[s + 1] - begins[s]; lse, dmin [n][h][w] scratch; E [T + n] (E_n per slot, then E_0 per sample);
+// g [n][h][gpitch] (zeros from column w on); loss[0] and nonfinite[0] (optional) as the head's reduction writes them.
+// passes: bits (1 normaliser, 2 expectation, 4 gradient and loss), 7 = the loss
+int can_bayes_loss(const float* et, const float* pts, const long long* begins, const int* cnt, int n, int h, int w,
+                   long long T, int max_count, float sigma, float rho, int ch, int cw, int d, float* lse, float* dmin,
+                   float* E, float* g, int gpitch, float* loss, float* nonfinite, int passes, void* stream);
+// the head backward for a given g [P] fp32 (indexed and padded like can_head_train's gt): dy, and dw / db through
+// can_head_reduce (scratch: one float for its loss slot); no flag is written
+int can_head_bwd(const void* y, const float* w, const float* g, void* dy, float* part, int nblk, float* dw, float* db,
+                 float* scratch, int P, float gscale, float beta, const float* lscale, int dt, void* stream);
+int can_head_reduce(const float* part, int nblk, float* dw, float* db, float* loss, float beta, float* nonfinite,
+                    void* stream);
+
 // preprocess.hip
 int can_preprocess_image(const void* img, int H0, int W0, int C, int flip, void* out, int Ho, int Wo, int dt,
                          void* stream);

@@ -1023,6 +1023,14 @@ extern "C" int can_head_train(const void* y, const float* w, const float* b, con
   return (int)hipGetLastError();
 }
 
+// the head's reduction alone, for a kernel that writes head_train_kernel's part[nblk][66] itself (bayes.hip head_bwd)
+extern "C" int can_head_reduce(const float* part, int nblk, float* dw, float* db, float* loss, float beta,
+                               float* nonfinite, void* stream) {
+  hipLaunchKernelGGL(head_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, part, nblk, dw, db, loss, beta,
+                     nonfinite);
+  return (int)hipGetLastError();
+}
+
 extern "C" int can_sgd_momentum(float* p, float* buf, const float* g, size_t n, float lr, float momentum,
                                 float gscale, int first, float* flags, const float* lr_dev, void* stream,
                                 const float* gmul) {

@@ -701,6 +701,50 @@ class CANNetExecutor(ContextSchedule):
                           self._stream(), w if wv else 0, wv, *(() if wt is None else (wt.data_ptr(),)))
         return loss, (et[..., :wv] if wv else et), d_b6
 
+    def head_bwd(self, b6, g, grads, gscale: float = 1.0, beta: float = 0.0, lscale: Optional[torch.Tensor] = None):
+        """The head's backward for a given g = dL/d(et), fp32 [n,1,h,w] at b6's pitch (zero in padding columns):
+        d(b6 pre-act) (ReLU-masked, times lscale) and the head gradients (written, or accumulated with beta = 1), the
+        lane layout and reductions of head_train.  Writes no flag.  Returns d_b6."""
+        n, h, w, c = b6.shape
+        if g.dtype != torch.float32 or g.numel() != n * h * w or not g.is_contiguous():
+            raise ValueError(f"g must be a contiguous fp32 [{n}, 1, {h}, {w}], got {tuple(g.shape)} {g.dtype}")
+        P = n * h * w
+        d_b6 = torch.empty_like(b6)
+        nblk = max(1, min(1024, (P * 8 + 255) // 256))
+        part = torch.empty(nblk * 66 + 1, dtype=torch.float32, device=b6.device)    # (+ the reduction's loss slot)
+        self.C.head_bwd(b6.data_ptr(), self.head.weight.detach().data_ptr(), g.data_ptr(), d_b6.data_ptr(),
+                        part.data_ptr(), nblk, grads[self.head_w_index].data_ptr(),
+                        grads[self.head_b_index].data_ptr(), part.data_ptr() + 4 * nblk * 66, P, float(gscale),
+                        float(beta), lscale.data_ptr() if lscale is not None else 0, self.dt, self._stream())
+        return d_b6
+
+    def head_train_bayes(self, b6, target, grads, gscale: float = 1.0, beta: float = 0.0,
+                         lscale: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None,
+                         wvalid: Optional[int] = None, sigma: float = 8.0, bg_ratio: float = 0.15):
+        """head_train with the Bayesian point loss (ops/bayes.py, README "Bayesian loss") in the place of the MSE:
+        head_fwd -> normaliser, expectation and gradient passes against ``target`` (a PointTarget) -> head_bwd.
+        Returns (loss, et, d_b6) and writes flags[1] / flags[0] like head_train.  A width-padded b6: the loss sees the
+        valid width, g is zero in the padding columns."""
+        from . import bayes
+        bayes._check_params(sigma, bg_ratio)
+        n, h, w, c = b6.shape
+        wvalid = self.last_wvalid if wvalid is None else wvalid
+        wv = C._wv(wvalid, w)
+        wg = wv or w
+        if tuple(target.shape) != ("points", n, h, wg):
+            raise ValueError(f"target {tuple(target.shape)} != {('points', n, h, wg)}")
+        et = self.head_forward(b6, wvalid)                    # dense at the valid width
+        g = torch.empty(n, 1, h, w, dtype=torch.float32, device=b6.device)
+        if flags is not None:
+            if not (flags.dtype == torch.float32 and flags.is_contiguous() and flags.numel() >= 2):
+                raise ValueError("flags must be a contiguous fp32 vector of >= 2 elements")
+            loss, nf = flags[1:2], flags.data_ptr()
+        else:
+            loss, nf = torch.empty(1, dtype=torch.float32, device=b6.device), 0
+        bayes._launch_loss(self.C, et, target, sigma, bg_ratio, g, w, loss.data_ptr(), nf)
+        d_b6 = self.head_bwd(b6, g, grads, gscale=gscale, beta=beta, lscale=lscale)
+        return loss, et, d_b6
+
     # ----------------------------------------------------------- autograd entry
     def __call__(self, img: torch.Tensor) -> torch.Tensor:
         if not torch.is_grad_enabled() or not any(p.requires_grad for p in self._params()):

@@ -231,12 +231,14 @@ def _unpack(packed):
     return buf, (n, ho, wo, goff, doff), KINDS[len(meta) - 5]
 
 
-def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device, roi=False):
+def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device, roi=False, points=False):
     """The one launch of a pack of any kind: d, the device copy of buf -> (x4, gt), gt a view of d.  The crop entries
     check the host descriptors (in buf) before they launch, the photo entry the host photo rows as well.
     roi: the pack's images are 4-channel with the ROI mask as alpha (CrowdDataset(roi=True)); after the pack's other
     launches, on the same stream, roi_weights_kernel writes gt2 [n,2,ho/d,wo/d] (the ground truth, the loss weights)
-    and (x4, gt2) is returned.  Its check runs on the host descriptors before ANY launch."""
+    and (x4, gt2) is returned.  Its check runs on the host descriptors before ANY launch.
+    points (a heads pack only): after the pack's launches, on the same stream, crop_points_kernel (csrc/bayes.hip) writes
+    the heads of every crop as points and (x4, PointTarget) is returned (README, "Bayesian loss")."""
     hd, wd = ho // downsample, wo // downsample
     gt = d[goff:goff + 4 * n * hd * wd].view(torch.float32).view(n, 1, hd, wd)
     desc = d[doff:doff + 64 * n].view(torch.int64).view(n, 8)
@@ -244,6 +246,8 @@ def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device, r
     tail = (ho, wo, downsample, dt_code(dtype), _ext.stream_ptr(device))
     kind, *flags = kind.split("+")
     heads, photo = "heads" in flags, "photo" in flags
+    if points and (roi or not heads):
+        raise ValueError("points=True takes a heads pack (PackedCollate(gt_from_heads=True)) without ROI masks")
     poff = buf.numel() - (4 * PackedCollate.PHOTO_ROW * n if photo else 0)      # the photo region ends the buffer
     if roi:
         rc = C.roi_weights_check(buf.data_ptr() + doff, n, goff, ho, wo, downsample)
@@ -270,6 +274,11 @@ def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device, r
     if heads:
         C.gt_from_heads(d.data_ptr() + hoff, d.data_ptr() + roff, desc.data_ptr(), buf.data_ptr() + hoff, nh,
                         buf.data_ptr() + roff, buf.data_ptr() + doff, n, gt.data_ptr(), ho, wo, downsample, tail[-1])
+    if points:
+        from .bayes import crop_points
+        return x4, crop_points(d[hoff:hoff + 16 * nh].view(torch.float32).view(nh, 4),
+                               d[roff:roff + 16 * n].view(torch.int64).view(n, 2), desc, n, ho, wo, downsample,
+                               counts=buf[roff:roff + 16 * n].view(torch.int64)[1::2].tolist(), stream=tail[-1])
     if roi:
         gt2 = torch.empty(n, 2, hd, wd, dtype=torch.float32, device=device)
         C.roi_weights(d.data_ptr(), goff, desc.data_ptr(), buf.data_ptr() + doff, n, gt.data_ptr(), gt2.data_ptr(),
@@ -279,12 +288,13 @@ def _launch(C, kind, buf, d, n, ho, wo, goff, doff, downsample, dtype, device, r
 
 
 def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = torch.bfloat16,
-                      copy_stream=None, roi: bool = False):
+                      copy_stream=None, roi: bool = False, points: bool = False):
     """PackedCollate output -> (x4 [N,Ho,Wo,4] 16-bit NHWC4, gt [N,1,Ho/d,Wo/d] fp32): one copy of the packed buffer
     and one launch for the whole batch of images.  copy_stream: a torch.cuda.Stream the H2D copy is issued on (the
     compute stream then waits for it): a pinned copy queued behind the previous step's kernels on the compute stream
     held the host ~0.6 ms per step at batch 1 (profiles/r5/host/), one on an idle copy stream does not.
-    roi=True (a CrowdDataset(roi=True) pack): returns (x4, gt2 [N,2,Ho/d,Wo/d]), the loss weights in channel 1."""
+    roi=True (a CrowdDataset(roi=True) pack): returns (x4, gt2 [N,2,Ho/d,Wo/d]), the loss weights in channel 1.
+    points=True (a heads pack): returns (x4, PointTarget), the crops' heads as points (ops/bayes.py)."""
     C = _ext.require()
     buf, dims, kind = _unpack(packed)
     dev = torch.device(device)
@@ -296,7 +306,7 @@ def preprocess_packed(packed, device, downsample: int = 8, dtype: torch.dtype = 
         d.record_stream(cur)              # allocated on the copy stream, consumed on the compute stream
     else:
         d = buf.to(dev, non_blocking=True)
-    return _launch(C, kind, buf, d, *dims, downsample, dtype, dev, roi=roi)
+    return _launch(C, kind, buf, d, *dims, downsample, dtype, dev, roi=roi, **(dict(points=True) if points else {}))
 
 
 class AheadPrep:
@@ -309,8 +319,10 @@ class AheadPrep:
     nothing: with preprocess_packed(copy_stream=...) the kernel ran on the compute stream behind a wait for the copy.
     """
 
-    def __init__(self, device, dtype: torch.dtype = torch.bfloat16, downsample: int = 8, roi: bool = False):
+    def __init__(self, device, dtype: torch.dtype = torch.bfloat16, downsample: int = 8, roi: bool = False,
+                 points: bool = False):
         self.roi = bool(roi)                  # the packs carry ROI masks: gt comes back [n, 2, h, w] (_launch)
+        self.points = bool(points)            # heads packs: the target comes back a PointTarget (_launch)
         self.device = torch.device(device)
         self.dtype = dtype
         self.ds = downsample
@@ -325,7 +337,8 @@ class AheadPrep:
         with torch.cuda.stream(self.copy):
             d = buf.to(self.device, non_blocking=True)
             with _ext.launch_on(self.copy.cuda_stream):
-                x4, gt = _launch(C, kind, buf, d, *dims, self.ds, self.dtype, self.device, roi=self.roi)
+                x4, gt = _launch(C, kind, buf, d, *dims, self.ds, self.dtype, self.device, roi=self.roi,
+                                 **(dict(points=True) if self.points else {}))
             ev = torch.cuda.Event()
             ev.record(self.copy)
         return x4, gt, d, ev
@@ -336,6 +349,6 @@ class AheadPrep:
         cur.wait_event(ev)
         x4.record_stream(cur)
         d.record_stream(cur)                  # (gt is a view of d, or with roi a tensor of its own)
-        if self.roi:
+        if self.roi or self.points:
             gt.record_stream(cur)
         return x4, gt

@@ -124,6 +124,20 @@ def game_level(v):
     return n
 
 
+def bayes_sigma(v):
+    x = float(v)
+    if not 0.0 < x < float("inf"):
+        raise argparse.ArgumentTypeError(f"--bayes-sigma must be > 0, got {v!r}")
+    return x
+
+
+def bayes_bg(v):
+    x = float(v)
+    if not 0.0 <= x <= 1.0:
+        raise argparse.ArgumentTypeError(f"--bayes-bg must be in [0, 1] (0 = no background class), got {v!r}")
+    return x
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -141,6 +155,17 @@ class _Parser(argparse.ArgumentParser):
                 self.error(f"{flag} jitters the crops of decoded dataset images; it cannot be combined with --synthetic")
             if value is not None and ns.crop_size is None:
                 self.error(f"{flag} jitters the colours of the crops of --crop-size; give --crop-size as well")
+        if ns.loss == "bayes":
+            for bad, why in ((not ns.gt_from_heads, "reads the head records of --gt-from-heads; give --gt-from-heads"),
+                             (ns.impl == "torch", "runs on the native step only; it cannot be combined with --impl torch"),
+                             (ns.dtype == "fp32", "runs on the native bf16 / fp16 step; it cannot be combined with "
+                                                  "--dtype fp32"),
+                             (not ns.gpu_preprocess, "takes its points from the GPU input pipeline; it cannot be "
+                                                     "combined with --gpu-preprocess 0"),
+                             (ns.roi_masks, "has no per-cell weights; it cannot be combined with --roi-masks"),
+                             (ns.graph is True, "changes its target per step; it cannot be combined with --graph 1")):
+                if bad:
+                    self.error(f"--loss bayes {why}")
         return ns
 
 
@@ -255,6 +280,15 @@ def build_parser():
     p.add_argument("--eval-game", type=game_level, default=None, metavar="L",
                    help="evaluate with the grid average mean absolute error GAME(1..L) as well (0 <= L <= 3; GAME(0) "
                         "is the MAE), logged as game1..gameL next to mae and rmse.  Default: off")
+    p.add_argument("--loss", choices=["mse", "bayes"], default="mse",
+                   help="mse (default): the sum-reduced MSE against the density map.  bayes: the Bayesian point loss "
+                        "(Ma et al., ICCV 2019) against the head records of --gt-from-heads, sum over samples of "
+                        "sum_n |1 - E_n| + |E_0|; native step only (README, 'Bayesian loss').  Evaluation is unchanged")
+    p.add_argument("--bayes-sigma", type=bayes_sigma, default=8.0,
+                   help="with --loss bayes: the width of the heads' likelihood in crop pixels (> 0)")
+    p.add_argument("--bayes-bg", type=bayes_bg, default=0.15,
+                   help="with --loss bayes: the background class's distance as a fraction of the crop's shorter side "
+                        "(0 <= R <= 1; 0 = no background class)")
     p.add_argument("--log-every", type=int, default=20,
                    help="steps between the training records of --log-jsonl (each reads the loss back: a host sync)")
     return p
@@ -343,7 +377,8 @@ def main(args):
         copy_stream = torch.cuda.Stream(device) if torch.device(device).type == "cuda" else None
         roi_kw = dict(roi=True) if args.roi_masks else {}    # the packs carry the masks as alpha: gt [n, 2, h, w]
         prep = lambda b: preprocess_packed(b, device, dtype=act, copy_stream=copy_stream, **roi_kw)  # noqa: E731
-        train_prep = AheadPrep(device, dtype=act, **roi_kw)  # training: the next batch one step ahead
+        # training: the next batch one step ahead; --loss bayes: its target is the crops' heads as points
+        train_prep = AheadPrep(device, dtype=act, **roi_kw, **(dict(points=True) if args.loss == "bayes" else {}))
 
     model = CANNet(vgg16_path=args.vgg16 or None, backend="hip" if args.impl == "hip" else "torch",
                    batch_norm=args.batch_norm)
@@ -362,6 +397,8 @@ def main(args):
     opt = dict(optimizer=args.optimizer, momentum=args.momentum, weight_decay=args.weight_decay,
                betas=(args.beta1, args.beta2), eps=args.eps, accum_steps=args.accum_steps,
                clip_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+    if args.loss == "bayes":
+        opt.update(loss="bayes", bayes_sigma=args.bayes_sigma, bayes_bg=args.bayes_bg)
     ema_on = args.ema_decay > 0
     if native:
         stepper = build_trainer(impl="hip", dtype=args.dtype, device=device, world=world, lr=base_lr, graph=graph,
@@ -473,7 +510,9 @@ def main(args):
                     **(dict(photo_jitter=list(args.photo_jitter)) if args.photo_jitter is not None else {}),
                     **(dict(gray_prob=args.gray_prob) if args.gray_prob is not None else {}),
                     **(dict(ema_decay=args.ema_decay) if ema_on else {}),
-                    **(dict(roi_masks=True) if args.roi_masks else {}), **extra)
+                    **(dict(roi_masks=True) if args.roi_masks else {}),
+                    **(dict(loss_fn="bayes", bayes_sigma=args.bayes_sigma, bayes_bg=args.bayes_bg)
+                       if args.loss == "bayes" else {}), **extra)
             if use_wandb:
                 wandb_log(loss=mean_loss, mae=mean_mae, lr=lr_now)
         barrier()
