@@ -141,6 +141,18 @@ int can_head_bwd(const void* y, const float* w, const float* g, void* dy, float*
 int can_head_reduce(const float* part, int nblk, float* dw, float* db, float* loss, float beta, float* nonfinite,
                     void* stream);
 
+// otloss.hip: the DM-Count loss on head records (README, "DM-Count loss"): count, entropic OT (iters Sinkhorn iterations
+// as two MFMA GEMMs each) and total variation.  et [n][h][w] dense against a PointTarget's pts / begins / cnt; tile (16,
+// 32 or 64) the heads per iteration block; scratch: Ar [T][wp], Br [T][hp] (hp, wp: h, w rounded up to 16), u, a, q,
+// beta [n][h][w], v [T], Pb [n], part [n][ceil(max_count / tile)][h][w]; g [n][h][gpitch] (zeros from column w on),
+// terms [n][3] = (L_c, L_ot, L_tv), loss[0] and nonfinite[0] (optional) as the head's reduction writes them.  All
+// arguments are checked before the first launch: -2 out of range (1 <= eps <= 100, 1 <= iters <= 1000, weights finite
+// and >= 0), -41 a map too large for the iteration kernel's LDS.
+int can_dmcount_loss(const float* et, const float* pts, const long long* begins, const int* cnt, int n, int h, int w,
+                     long long T, int max_count, int tile, float eps, int iters, float w_ot, float w_tv, int ch, int cw,
+                     int d, float* Ar, float* Br, float* u, float* v, float* a, float* q, float* beta, float* Pb,
+                     float* part, float* g, int gpitch, float* terms, float* loss, float* nonfinite, void* stream);
+
 // preprocess.hip
 int can_preprocess_image(const void* img, int H0, int W0, int C, int flip, void* out, int Ho, int Wo, int dt,
                          void* stream);

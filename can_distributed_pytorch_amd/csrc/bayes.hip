@@ -42,15 +42,6 @@ __device__ __forceinline__ float bl_bg(float dmin, float D, float k) {
   const float q = D - dmin;
   return __fmul_rn(k, __fmul_rn(q, q));
 }
-__device__ __forceinline__ float bl_sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-// sum over the block's 256 threads, fixed order: butterfly per wave, then the four waves in order (every thread calls)
-__device__ __forceinline__ float bl_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // One block per output sample.  A record (c, r, ., .) is in the window iff x0 <= c < x0 + sw and y0 <= r < y0 + sh; an
 // unscaled crop (slot 7 == 1) uses crop_window's valid extent as the window and maps onto it, as gt_from_heads_kernel

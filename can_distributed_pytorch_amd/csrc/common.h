@@ -134,6 +134,16 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// the point losses' helpers (bayes.hip, otloss.hip)
+__device__ __forceinline__ float bl_sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+// sum over the block's 256 threads, fixed order: butterfly per wave, then the four waves in order (every thread calls)
+__device__ __forceinline__ float bl_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
 
 // Bias-gradient partials from a conv epilogue: lane (fr = lane & 15, fq = lane >> 4) holds 16 per-channel
 // sums bs[0..15] over its pixels; the 16 lanes of a row (same fq, same channels) are summed by a

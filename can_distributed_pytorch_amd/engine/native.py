@@ -57,6 +57,9 @@ re-designed for MI355X:
 * ``loss="bayes"`` trains on the Bayesian point loss: ``step(img, target)`` takes the crops' heads as an
   ``ops.bayes.PointTarget`` and the fused head is ``executor.head_train_bayes`` (head forward, the loss's three passes,
   head backward); everything after the head is the same step.  Eager only (README "Bayesian loss").
+* ``loss="dmcount"`` is the same step on the DM-Count loss (count, entropic OT and total-variation terms):
+  ``executor.head_train_dmcount``, parameters ``ot_reg``, ``ot_iters``, ``ot_weight``, ``tv_weight``.  Eager only
+  (README "DM-Count loss").
 
 CU budget of the gradient all-reduce (``comm_ctas``, default 8 = parallel.reducer.DEFAULT_COMM_CTAS): the owned RCCL
 communicator is created with ncclConfig_t.minCTAs = maxCTAs = comm_ctas, so its kernels occupy exactly that many of
@@ -165,7 +168,8 @@ class SplitCapture:
 
 
 OPTIMIZERS = ("sgd", "adam", "adamw")
-LOSSES = ("mse", "bayes")                        # bayes: step(img, target) takes an ops.bayes.PointTarget
+LOSSES = ("mse", "bayes", "dmcount")
+POINT_LOSSES = ("bayes", "dmcount")              # step(img, target) takes an ops.bayes.PointTarget
 
 
 class NativeStepper:
@@ -175,21 +179,27 @@ class NativeStepper:
                  graph_max_shapes: int = 8, comm_ctas: Optional[int] = None, graph_bind_inputs: bool = False,
                  optimizer: str = "sgd", weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  accum_steps: int = 1, clip_grad_norm: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True,
-                 loss: str = "mse", bayes_sigma: float = 8.0, bayes_bg: float = 0.15):
+                 loss: str = "mse", bayes_sigma: float = 8.0, bayes_bg: float = 0.15, ot_reg: float = 10.0,
+                 ot_iters: int = 100, ot_weight: float = 0.1, tv_weight: float = 0.01):
         check_ema_decay(ema_decay)
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
-        if loss == "bayes":
+        if loss in POINT_LOSSES:
             # step(img, target) takes a PointTarget: its pointers and counts change per step, so there is nothing a
             # captured step could replay ("auto" runs eagerly)
             if graph is True:
-                raise ValueError("loss='bayes' cannot run as a captured step (graph=True): the point target changes "
+                raise ValueError(f"loss={loss!r} cannot run as a captured step (graph=True): the point target changes "
                                  "per step; use graph=False")
-            if not bayes_sigma > 0 or not 0 <= bayes_bg <= 1:
+            if loss == "bayes" and (not bayes_sigma > 0 or not 0 <= bayes_bg <= 1):
                 raise ValueError(f"bayes_sigma must be > 0 and bayes_bg in [0, 1], got {bayes_sigma!r}, {bayes_bg!r}")
+            if loss == "dmcount":
+                from ..ops.dmcount import _check_params
+                _check_params(ot_reg, ot_iters, ot_weight, tv_weight)
             graph = False
         self.loss = loss
         self.bayes_sigma, self.bayes_bg = float(bayes_sigma), float(bayes_bg)
+        self.dmcount = dict(reg=float(ot_reg), iters=int(ot_iters), ot_weight=float(ot_weight),
+                            tv_weight=float(tv_weight))
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         if int(accum_steps) != accum_steps or accum_steps < 1:
@@ -345,6 +355,8 @@ class NativeStepper:
             if self.loss == "bayes":
                 loss, et, d_b6 = ex.head_train_bayes(b6, gt, self.grads, sigma=self.bayes_sigma,
                                                      bg_ratio=self.bayes_bg, **head)
+            elif self.loss == "dmcount":
+                loss, et, d_b6 = ex.head_train_dmcount(b6, gt, self.grads, **self.dmcount, **head)
             else:
                 loss, et, d_b6 = ex.head_train(b6, gt, self.grads, **head)
         red = self.reducer if phase[1] else None
@@ -464,8 +476,8 @@ class NativeStepper:
         non-finite flag, Adam's step count and the fp16 loss scale all advance per window."""
         if self._ema_in:
             raise RuntimeError("step() inside ema_weights(): the model holds the averaged weights")
-        if (self.loss == "bayes") != (getattr(gt, "shape", ("",))[:1] == ("points",)):
-            raise TypeError("loss='bayes' steps on (img, PointTarget), loss='mse' on (img, gt map)")
+        if (self.loss in POINT_LOSSES) != (getattr(gt, "shape", ("",))[:1] == ("points",)):
+            raise TypeError("loss='bayes' and 'dmcount' step on (img, PointTarget), loss='mse' on (img, gt map)")
         if img.device != self.device:
             img = img.to(self.device, non_blocking=True)
         if gt.device != self.device:

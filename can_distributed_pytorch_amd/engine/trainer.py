@@ -419,14 +419,19 @@ def build_trainer(impl="hip", dtype="bf16", device="cuda", world=1, lr=1e-7, bat
                   graph_bind_inputs: bool = False, graph_max_shapes: int = 8, optimizer: str = "sgd",
                   momentum: float = 0.95, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
                   accum_steps: int = 1, clip_grad_norm: float = 0.0, ema_decay: float = 0.0,
-                  ema_warmup: bool = True, loss: str = "mse", bayes_sigma: float = 8.0, bayes_bg: float = 0.15):
+                  ema_warmup: bool = True, loss: str = "mse", bayes_sigma: float = 8.0, bayes_bg: float = 0.15,
+                  ot_reg: float = 10.0, ot_iters: int = 100, ot_weight: float = 0.1, tv_weight: float = 0.01):
     opt = dict(optimizer=optimizer, momentum=momentum, weight_decay=weight_decay, betas=betas, eps=eps,
                accum_steps=accum_steps, clip_grad_norm=clip_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
     if loss != "mse":
-        # the Bayesian point loss exists on the native bf16 / fp16 step alone (README "Bayesian loss")
+        # the point losses exist on the native bf16 / fp16 step alone (README "Bayesian loss", "DM-Count loss")
         if impl != "hip" or dtype == "fp32":
             raise ValueError(f"loss={loss!r} needs the native step (impl='hip', dtype bf16 or fp16)")
-        opt.update(loss=loss, bayes_sigma=bayes_sigma, bayes_bg=bayes_bg)
+        opt.update(loss=loss)
+        if loss == "bayes":
+            opt.update(bayes_sigma=bayes_sigma, bayes_bg=bayes_bg)
+        else:
+            opt.update(ot_reg=ot_reg, ot_iters=ot_iters, ot_weight=ot_weight, tv_weight=tv_weight)
     if impl == "arena":
         return ArenaStepper(device, world=world, lr=lr, model=model, bucket_mb=bucket_mb, **opt)
     if impl == "torch":

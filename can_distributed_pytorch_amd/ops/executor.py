@@ -727,6 +727,26 @@ class CANNetExecutor(ContextSchedule):
         valid width, g is zero in the padding columns."""
         from . import bayes
         bayes._check_params(sigma, bg_ratio)
+        return self._head_train_points(
+            b6, target, grads, gscale, beta, lscale, flags, wvalid,
+            lambda et, g, w, loss, nf: bayes._launch_loss(self.C, et, target, sigma, bg_ratio, g, w, loss, nf))
+
+    def head_train_dmcount(self, b6, target, grads, gscale: float = 1.0, beta: float = 0.0,
+                           lscale: Optional[torch.Tensor] = None, flags: Optional[torch.Tensor] = None,
+                           wvalid: Optional[int] = None, reg: float = 10.0, iters: int = 100, ot_weight: float = 0.1,
+                           tv_weight: float = 0.01):
+        """head_train with the DM-Count loss (ops/dmcount.py, README "DM-Count loss") in the place of the MSE:
+        head_fwd -> setup, 2 iters Sinkhorn launches and the tail against ``target`` (a PointTarget) -> head_bwd.
+        Returns, flags and a width-padded b6 as head_train_bayes."""
+        from . import dmcount
+        dmcount._check_params(reg, iters, ot_weight, tv_weight)
+        return self._head_train_points(
+            b6, target, grads, gscale, beta, lscale, flags, wvalid,
+            lambda et, g, w, loss, nf: dmcount._launch_loss(self.C, et, target, reg, iters, ot_weight, tv_weight, g, w,
+                                                            loss, nf))
+
+    def _head_train_points(self, b6, target, grads, gscale, beta, lscale, flags, wvalid, launch_loss):
+        """head_fwd -> launch_loss(et, g, g's pitch, loss pointer, flag pointer) -> head_bwd: the head of a point loss."""
         n, h, w, c = b6.shape
         wvalid = self.last_wvalid if wvalid is None else wvalid
         wv = C._wv(wvalid, w)
@@ -741,7 +761,7 @@ class CANNetExecutor(ContextSchedule):
             loss, nf = flags[1:2], flags.data_ptr()
         else:
             loss, nf = torch.empty(1, dtype=torch.float32, device=b6.device), 0
-        bayes._launch_loss(self.C, et, target, sigma, bg_ratio, g, w, loss.data_ptr(), nf)
+        launch_loss(et, g, w, loss.data_ptr(), nf)
         d_b6 = self.head_bwd(b6, g, grads, gscale=gscale, beta=beta, lscale=lscale)
         return loss, et, d_b6
 

@@ -138,6 +138,27 @@ def bayes_bg(v):
     return x
 
 
+def ot_reg(v):
+    x = float(v)
+    if not 1.0 <= x <= 100.0:
+        raise argparse.ArgumentTypeError(f"--ot-reg must be in [1, 100] (plain-domain Sinkhorn), got {v!r}")
+    return x
+
+
+def ot_iters(v):
+    n = int(v)
+    if not 1 <= n <= 1000:
+        raise argparse.ArgumentTypeError(f"--ot-iters must be in [1, 1000], got {v!r}")
+    return n
+
+
+def loss_weight(v):
+    x = float(v)
+    if not 0.0 <= x < float("inf"):
+        raise argparse.ArgumentTypeError(f"a loss weight must be finite and >= 0, got {v!r}")
+    return x
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -155,7 +176,7 @@ class _Parser(argparse.ArgumentParser):
                 self.error(f"{flag} jitters the crops of decoded dataset images; it cannot be combined with --synthetic")
             if value is not None and ns.crop_size is None:
                 self.error(f"{flag} jitters the colours of the crops of --crop-size; give --crop-size as well")
-        if ns.loss == "bayes":
+        if ns.loss != "mse":
             for bad, why in ((not ns.gt_from_heads, "reads the head records of --gt-from-heads; give --gt-from-heads"),
                              (ns.impl == "torch", "runs on the native step only; it cannot be combined with --impl torch"),
                              (ns.dtype == "fp32", "runs on the native bf16 / fp16 step; it cannot be combined with "
@@ -165,7 +186,7 @@ class _Parser(argparse.ArgumentParser):
                              (ns.roi_masks, "has no per-cell weights; it cannot be combined with --roi-masks"),
                              (ns.graph is True, "changes its target per step; it cannot be combined with --graph 1")):
                 if bad:
-                    self.error(f"--loss bayes {why}")
+                    self.error(f"--loss {ns.loss} {why}")
         return ns
 
 
@@ -280,15 +301,25 @@ def build_parser():
     p.add_argument("--eval-game", type=game_level, default=None, metavar="L",
                    help="evaluate with the grid average mean absolute error GAME(1..L) as well (0 <= L <= 3; GAME(0) "
                         "is the MAE), logged as game1..gameL next to mae and rmse.  Default: off")
-    p.add_argument("--loss", choices=["mse", "bayes"], default="mse",
+    p.add_argument("--loss", choices=["mse", "bayes", "dmcount"], default="mse",
                    help="mse (default): the sum-reduced MSE against the density map.  bayes: the Bayesian point loss "
                         "(Ma et al., ICCV 2019) against the head records of --gt-from-heads, sum over samples of "
-                        "sum_n |1 - E_n| + |E_0|; native step only (README, 'Bayesian loss').  Evaluation is unchanged")
+                        "sum_n |1 - E_n| + |E_0|; native step only (README, 'Bayesian loss').  dmcount: DM-Count (Wang et "
+                        "al., NeurIPS 2020) against the same records, |N - P| + w_ot L_ot + w_tv L_tv with P = sum |et|; "
+                        "native step only (README, 'DM-Count loss').  Evaluation is unchanged")
     p.add_argument("--bayes-sigma", type=bayes_sigma, default=8.0,
                    help="with --loss bayes: the width of the heads' likelihood in crop pixels (> 0)")
     p.add_argument("--bayes-bg", type=bayes_bg, default=0.15,
                    help="with --loss bayes: the background class's distance as a fraction of the crop's shorter side "
                         "(0 <= R <= 1; 0 = no background class)")
+    p.add_argument("--ot-reg", type=ot_reg, default=10.0,
+                   help="with --loss dmcount: the entropic regularisation of the transport term (1 <= E <= 100)")
+    p.add_argument("--ot-iters", type=ot_iters, default=100,
+                   help="with --loss dmcount: the number of Sinkhorn iterations, fixed (1 <= T <= 1000)")
+    p.add_argument("--ot-weight", type=loss_weight, default=0.1,
+                   help="with --loss dmcount: the weight of the transport term (>= 0)")
+    p.add_argument("--tv-weight", type=loss_weight, default=0.01,
+                   help="with --loss dmcount: the weight of the total-variation term (>= 0)")
     p.add_argument("--log-every", type=int, default=20,
                    help="steps between the training records of --log-jsonl (each reads the loss back: a host sync)")
     return p
@@ -377,8 +408,8 @@ def main(args):
         copy_stream = torch.cuda.Stream(device) if torch.device(device).type == "cuda" else None
         roi_kw = dict(roi=True) if args.roi_masks else {}    # the packs carry the masks as alpha: gt [n, 2, h, w]
         prep = lambda b: preprocess_packed(b, device, dtype=act, copy_stream=copy_stream, **roi_kw)  # noqa: E731
-        # training: the next batch one step ahead; --loss bayes: its target is the crops' heads as points
-        train_prep = AheadPrep(device, dtype=act, **roi_kw, **(dict(points=True) if args.loss == "bayes" else {}))
+        # training: the next batch one step ahead; --loss bayes / dmcount: its target is the crops' heads as points
+        train_prep = AheadPrep(device, dtype=act, **roi_kw, **(dict(points=True) if args.loss != "mse" else {}))
 
     model = CANNet(vgg16_path=args.vgg16 or None, backend="hip" if args.impl == "hip" else "torch",
                    batch_norm=args.batch_norm)
@@ -399,6 +430,9 @@ def main(args):
                clip_grad_norm=args.clip_grad_norm, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
     if args.loss == "bayes":
         opt.update(loss="bayes", bayes_sigma=args.bayes_sigma, bayes_bg=args.bayes_bg)
+    elif args.loss == "dmcount":
+        opt.update(loss="dmcount", ot_reg=args.ot_reg, ot_iters=args.ot_iters, ot_weight=args.ot_weight,
+                   tv_weight=args.tv_weight)
     ema_on = args.ema_decay > 0
     if native:
         stepper = build_trainer(impl="hip", dtype=args.dtype, device=device, world=world, lr=base_lr, graph=graph,
@@ -512,7 +546,9 @@ def main(args):
                     **(dict(ema_decay=args.ema_decay) if ema_on else {}),
                     **(dict(roi_masks=True) if args.roi_masks else {}),
                     **(dict(loss_fn="bayes", bayes_sigma=args.bayes_sigma, bayes_bg=args.bayes_bg)
-                       if args.loss == "bayes" else {}), **extra)
+                       if args.loss == "bayes" else {}),
+                    **(dict(loss_fn="dmcount", ot_reg=args.ot_reg, ot_iters=args.ot_iters, ot_weight=args.ot_weight,
+                            tv_weight=args.tv_weight) if args.loss == "dmcount" else {}), **extra)
             if use_wandb:
                 wandb_log(loss=mean_loss, mae=mean_mae, lr=lr_now)
         barrier()
