@@ -418,6 +418,95 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional
                  _ext.stream_ptr(x.device), bx, brows)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Small-channel layers (csrc/conv_small.hip): Ci, Co multiples of 16, not both multiples of 64
+# ---------------------------------------------------------------------------------------------------------------------
+SMALL_MAX_DIL = 4
+
+
+def small_channels(ci: int, co: int) -> bool:
+    """Whether a ci -> co layer runs on the small-channel kernels: multiples of 16, at least one no multiple of 64."""
+    return ci % 16 == 0 and co % 16 == 0 and ci > 0 and co > 0 and (ci % 64 != 0 or co % 64 != 0)
+
+
+def _check_small(ci: int, co: int, ksize: int, dil: int):
+    if ci % 16 or co % 16 or ci < 16 or co < 16:
+        raise ValueError(f"small-channel conv needs Cin / Cout multiples of 16, got {ci} -> {co}")
+    if ksize not in (1, 3):
+        raise ValueError("ksize must be 1 or 3")
+    if not 1 <= dil <= SMALL_MAX_DIL:
+        raise ValueError(f"small-channel conv takes dilation 1 .. {SMALL_MAX_DIL}, got {dil}")
+
+
+def conv_small(x: torch.Tensor, wpack: torch.Tensor, bias: Optional[torch.Tensor], *, ksize: int, dil: int = 1,
+               epi: int = EPI_BIAS_RELU, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_igemm for channel counts that are multiples of 16: y[N,H,W,Co] = epi(conv(x[N,H,W,Ci], W)), stride 1,
+    'same' padding; wpack = pack_weight_fwd (forward) or pack_weight_dgrad (data gradient, epi=EPI_NONE);
+    epi EPI_BIAS_RELU / EPI_BIAS / EPI_NONE."""
+    C = _ext.require()
+    if x.dim() != 4:
+        raise ValueError("x must be [N,H,W,C]")
+    n, h, w, ci = x.shape
+    _check_act(x, "x")
+    co, k = wpack.shape
+    dt = x.dtype
+    if wpack.dtype != dt or not wpack.is_contiguous():
+        raise ValueError(f"wpack must be contiguous {dt}")
+    _check_small(ci, co, ksize, dil)
+    if k != ksize * ksize * ci:
+        raise ValueError(f"packed weight K={k} != {ksize}*{ksize}*{ci}")
+    if epi not in (EPI_BIAS_RELU, EPI_BIAS, EPI_NONE):
+        raise ValueError("small-channel conv takes EPI_BIAS_RELU, EPI_BIAS or EPI_NONE")
+    if epi != EPI_NONE:
+        if bias is None or bias.dtype != torch.float32 or bias.numel() != co or not bias.is_contiguous():
+            raise ValueError("bias must be contiguous fp32 [Cout]")
+    if out is None:
+        out = torch.empty(n, h, w, co, dtype=dt, device=x.device)
+    else:
+        if tuple(out.shape) != (n, h, w, co):
+            raise ValueError("out has the wrong shape")
+        _check_act(out, "out", dtype=dt)
+    for i0, i1 in image_chunks(n, h * w * max(ci, co)):
+        C.conv_small(x[i0:i1].data_ptr(), wpack.data_ptr(), bias.data_ptr() if epi != EPI_NONE else 0,
+                     out[i0:i1].data_ptr(), i1 - i0, h, w, ci, co, ksize, dil, epi, dt_code(dt),
+                     _ext.stream_ptr(x.device))
+    return out
+
+
+def conv_small_ws_floats(m: int, ci: int, co: int, ksize: int) -> int:
+    """fp32 workspace of conv_small_wgrad over m pixels: one dW + db partial per pixel slice (conv_small_plan.h)."""
+    return _ext.require().conv_small_slices(m, ci, co) * (co * ci * ksize * ksize + co)
+
+
+def conv_small_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor], *, ksize: int,
+                     dil: int = 1, ws: Optional[WgradWorkspace] = None, beta: float = 0.0, scale: float = 1.0) -> None:
+    """conv_wgrad for channel counts that are multiples of 16: dw[Co,Ci,kh,kw] (fp32, PyTorch layout) = scale *
+    sum_m dY[m,co] Xcol[m,k] (+ beta * dw), db likewise; partials per pixel slice, summed in slice order."""
+    C = _ext.require()
+    _check_act(dy, "dy")
+    _check_act(x, "x", dtype=dy.dtype)
+    if x.dim() != 4 or dy.dim() != 4:
+        raise ValueError("dy / x must be [N,H,W,C]")
+    n, h, w, ci = x.shape
+    co = dy.shape[-1]
+    if tuple(dy.shape[:3]) != (n, h, w):
+        raise ValueError("dy/x spatial mismatch")
+    _check_small(ci, co, ksize, dil)
+    if tuple(dw.shape) != (co, ci, ksize, ksize):
+        raise ValueError(f"dw shape {tuple(dw.shape)} != {(co, ci, ksize, ksize)}")
+    if dw.dtype != torch.float32 or not dw.is_contiguous():
+        raise ValueError("dw must be contiguous fp32")
+    if db is not None and (db.dtype != torch.float32 or db.numel() != co or not db.is_contiguous()):
+        raise ValueError("db must be contiguous fp32 [Co]")
+    ws = ws or WgradWorkspace(x.device)
+    # dW (and db) accumulate over image chunks: the first launch applies beta, the others add (beta = 1)
+    for c, (i0, i1) in enumerate(image_chunks(n, h * w * max(ci, co))):
+        buf = ws.reserve(conv_small_ws_floats((i1 - i0) * h * w, ci, co, ksize))
+        C.conv_small_wgrad(dy[i0:i1].data_ptr(), x[i0:i1].data_ptr(), buf.data_ptr(), buf.numel(), dw.data_ptr(),
+                           db.data_ptr() if db is not None else 0, i1 - i0, h, w, ci, co, ksize, dil,
+                           float(beta) if c == 0 else 1.0, float(scale), dt_code(dy.dtype), _ext.stream_ptr(x.device))
+
+
 def _ctx_wgrad_cus() -> int:
     """CUs the batched context 1x1 weight gradient is planned for.  It runs on the weight-gradient stream while the
     critical-path context backward (bilinear-transpose row / cell passes, ctx_bwd_final) runs on the compute stream;

@@ -8,7 +8,11 @@ GPU — and an autograd formula built from the native backward kernels.
   cannet::conv2d_nhwc(x, weight, bias, dilation, relu) -> y
       x [N,H,W,Ci] bf16/fp16 (NHWC, contiguous), weight [Co,Ci,k,k] fp32 master (k = 1 or 3), bias [Co] fp32 or
       None; stride 1, 'same' padding dilation*(k//2); y = [relu](conv(x, weight) + bias) in x.dtype.
-      Ci, Co multiples of 64 (the first 3-channel layer has its own kernel inside the executor).
+      Ci, Co multiples of 16 (the first 3-channel layer has its own kernel inside the executor).  When both are
+      multiples of 64 the op runs on the 64-channel-chunk kernels described next; otherwise (a 32-, 48- or 96-channel
+      stage, a 1x1 bottleneck to 16 channels, a 160-channel trunk ...) forward, data gradient and weight gradient run
+      on the small-channel MFMA kernels of csrc/conv_small.hip (``conv_small`` / ``conv_small_wgrad``: dilation 1..4,
+      same packs, same epilogues, same deterministic slice reduction), with no padding to 64 channels.
       Forward: conv_igemm (bias + ReLU epilogue).  Backward: dY masked by y > 0, the data gradient on the same
       kernel with the flipped / transposed weight pack, the weight + bias gradients on the split-pixel weight-
       gradient kernels (fp32, deterministic slab reduction) — the reference's nn.Conv2d + ReLU
@@ -50,8 +54,8 @@ def _conv_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     co, ci, k, _ = weight.shape
     if x.shape[-1] != ci:
         raise ValueError(f"x has {x.shape[-1]} channels, weight expects {ci}")
-    if ci % 64 or co % 64:
-        raise ValueError("cannet::conv2d_nhwc needs Ci and Co multiples of 64")
+    if ci % 16 or co % 16 or ci == 0 or co == 0:
+        raise ValueError("cannet::conv2d_nhwc needs Ci and Co multiples of 16")
     if x.dtype not in C.ACT_DTYPES:
         raise ValueError(f"x must be bf16 or fp16, got {x.dtype}")
     if weight.dtype != torch.float32:
@@ -76,6 +80,8 @@ def conv2d_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     else:
         bias = bias.detach().contiguous()
         epi = C.EPI_BIAS_RELU if relu else C.EPI_BIAS
+    if C.small_channels(ci, co):
+        return C.conv_small(x, wp, bias, ksize=k, dil=dilation, epi=epi)
     return C.conv_igemm(x, wp, bias, ksize=k, dil=dilation, epi=epi)
 
 
@@ -94,10 +100,11 @@ def conv2d_nhwc_backward(dy: torch.Tensor, x: torch.Tensor, y: torch.Tensor, wei
     if relu:
         dz = torch.where(y > 0, dz, torch.zeros((), dtype=dz.dtype, device=dz.device))
     dz = dz.contiguous()
-    dx = C.conv_igemm(dz, C.pack_weight_dgrad(weight, x.dtype), None, ksize=k, dil=dilation, epi=C.EPI_NONE)
+    conv, wgrad = (C.conv_small, C.conv_small_wgrad) if C.small_channels(ci, co) else (C.conv_igemm, C.conv_wgrad)
+    dx = conv(dz, C.pack_weight_dgrad(weight, x.dtype), None, ksize=k, dil=dilation, epi=C.EPI_NONE)
     dw = torch.empty(co, ci, k, k, dtype=torch.float32, device=x.device)
     db = torch.empty(co if need_bias else 0, dtype=torch.float32, device=x.device)
-    C.conv_wgrad(dz, x.contiguous(), dw, db if need_bias else None, ksize=k, dil=dilation)
+    wgrad(dz, x.contiguous(), dw, db if need_bias else None, ksize=k, dil=dilation)
     return dx, dw, db
 
 
