@@ -98,6 +98,21 @@ int can_grad_norm(const float* g, const long long* tab, int np, long long max_co
 int can_accum_tick(float* flags, float* acc, int fold, int close, void* stream);
 int can_img_to_nhwc4(const float* img, void* out, int N, int H, int W, int dt, void* stream);
 
+// batchnorm.hip: batch normalisation (+ ReLU) of an NHWC 16-bit map x [M][C] (M = N * H * W, C % 8 == 0), fixed-order
+// double partials part [S][2][C] (S pixel slices, 1 .. 65535; can_bn_slices: the planned count), fp32 parameters and
+// statistics.  Refused before any launch: -2 C, -3 training with M < 2, -4 eps negative or not finite, -5 a map beyond
+// the indexing, -6 a missing workspace / running statistic or S out of range, -7 a null operand, -20 dt.
+int can_bn_slices(long long M, int C);
+// stats [3][C] = (mean, biased var, rstd) of the batch (training) or from (rmean, rvar) (eval), ab [2][C] = (a, b) with
+// a = gamma * rstd, b = fma(-mean, a, beta); y = f2h(fma(x, a, b)), clamped at 0 with relu
+int can_bn_forward(const void* x, void* y, const float* gamma, const float* beta, const float* rmean, const float* rvar,
+                   double* part, int S, float* stats, float* ab, long long M, int C, double eps, int training, int relu,
+                   int dt, void* stream);
+// fin [4][C] = (dgamma, dbeta, c1, c2); dx = a (dz - c1 - xhat c2) (training) or a dz (eval), dz = dy where y > 0
+// (relu; y is read only then), xhat = (x - mean) rstd from the forward's stats
+int can_bn_backward(const void* dy, const void* x, const void* y, const float* gamma, const float* stats, double* part,
+                    int S, float* fin, void* dx, long long M, int C, int training, int relu, int dt, void* stream);
+
 // context.hip
 int can_ctx_reduce(int mode, const void* in0, const void* sdir, const void* dc, float* rowacc, float* cells, int N,
                    int h, int w, int C, int dt, void* stream, int wv);

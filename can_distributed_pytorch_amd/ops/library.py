@@ -22,6 +22,12 @@ GPU — and an autograd formula built from the native backward kernels.
       max); codes = int32 first-max one-hots (4 bits per channel, 0 where the window max is <= 0).  Backward
       scatters through the codes, so the ReLU's mask is part of the gradient: exactly the gradient of
       max_pool2d(relu(x)), and of a plain max-pool only where the input is already non-negative.
+  cannet::batch_norm_nhwc(x, weight, bias, running_mean, running_var, training, eps, relu) -> (y, stats)
+      nn.BatchNorm2d [+ ReLU] of an NHWC bf16/fp16 map, C % 8 == 0, fp32 parameters (csrc/batchnorm.hip): training
+      normalises with the batch statistics (double partial sums in a fixed order: bitwise repeatable), eval with
+      (running_mean, running_var).  Functional: the running buffers are never written; stats = fp32 [3, C] (mean,
+      biased variance, rstd), not differentiable, is what the backward and ``BatchNorm2dNHWC``'s buffer update use.
+      Backward: dz = dY masked by the stored y > 0, then dgamma / dbeta and dx on the native kernels.
   cannet::sgd_momentum_(param, momentum_buf, grad, lr, momentum, grad_scale) -> ()
       in-place fused SGD with momentum on contiguous fp32 tensors (torch.optim.SGD semantics, weight decay 0,
       dampening 0: buf = momentum * buf + grad_scale * grad; param -= lr * buf), one kernel.
@@ -31,7 +37,7 @@ GPU — and an autograd formula built from the native backward kernels.
       (decoupled=True) on contiguous fp32 tensors, one kernel; ``step`` is the 1-based step of this call (the bias
       corrections are 1 - beta^step); no amsgrad, no maximize.
 
-``Conv2dNHWC`` / ``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master parameters.
+``Conv2dNHWC`` / ``BatchNorm2dNHWC`` / ``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master parameters.
 """
 from __future__ import annotations
 
@@ -41,6 +47,7 @@ import torch
 import torch.nn as nn
 
 from . import _ext
+from . import batchnorm as BN
 from . import conv as C
 
 _LIB = "cannet"
@@ -167,6 +174,69 @@ def _pool_bwd(ctx, dy, dcodes):
 relu_max_pool2x2.register_autograd(_pool_bwd, setup_context=_pool_setup)
 
 
+def _bn_check(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_mean: Optional[torch.Tensor],
+              running_var: Optional[torch.Tensor], training: bool) -> int:
+    if x.dim() != 4:
+        raise ValueError("x must be NHWC [N,H,W,C]")
+    c = x.shape[-1]
+    if c == 0 or c % 8:
+        raise ValueError("cannet::batch_norm_nhwc needs C a multiple of 8")
+    if x.dtype not in C.ACT_DTYPES:
+        raise ValueError(f"x must be bf16 or fp16, got {x.dtype}")
+    vecs = [(weight, "weight"), (bias, "bias")]
+    if not training:
+        vecs += [(running_mean, "running_mean"), (running_var, "running_var")]
+    for t, name in vecs:
+        if t is None or t.dtype != torch.float32 or t.numel() != c:
+            raise ValueError(f"{name} must be fp32 [{c}]")
+    return c
+
+
+@torch.library.custom_op(f"{_LIB}::batch_norm_nhwc", mutates_args=())
+def batch_norm_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_mean: Optional[torch.Tensor],
+                    running_var: Optional[torch.Tensor], training: bool, eps: float = 1e-5,
+                    relu: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    _bn_check(x, weight, bias, running_mean, running_var, training)
+    return BN.bn_forward(x.contiguous(), weight, bias, running_mean, running_var, training, eps, relu)
+
+
+@batch_norm_nhwc.register_fake
+def _(x, weight, bias, running_mean, running_var, training, eps=1e-5, relu=True):
+    c = _bn_check(x, weight, bias, running_mean, running_var, training)
+    return x.new_empty(x.shape), x.new_empty(3, c, dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::batch_norm_nhwc_backward", mutates_args=())
+def batch_norm_nhwc_backward(dy: torch.Tensor, x: torch.Tensor, y: torch.Tensor, weight: torch.Tensor,
+                             stats: torch.Tensor, training: bool,
+                             relu: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of batch_norm_nhwc."""
+    dx, dg, db = BN.bn_backward(dy.to(x.dtype).contiguous(), x.contiguous(), y, weight, stats, training, relu)
+    return dx, dg.clone(), db.clone()           # dg / db are rows of one workspace tensor: outputs own their memory
+
+
+@batch_norm_nhwc_backward.register_fake
+def _(dy, x, y, weight, stats, training, relu):
+    return x.new_empty(x.shape), weight.new_empty(weight.shape), weight.new_empty(weight.shape)
+
+
+def _bn_setup(ctx, inputs, output):
+    x, weight, _, _, _, training, _, relu = inputs
+    y, stats = output
+    ctx.save_for_backward(x, y, weight, stats)
+    ctx.mark_non_differentiable(stats)
+    ctx.training, ctx.relu = training, relu
+
+
+def _bn_bwd(ctx, dy, dstats):
+    x, y, weight, stats = ctx.saved_tensors
+    dx, dg, db = batch_norm_nhwc_backward(dy, x, y, weight, stats, ctx.training, ctx.relu)
+    return dx, dg, db, None, None, None, None, None
+
+
+batch_norm_nhwc.register_autograd(_bn_bwd, setup_context=_bn_setup)
+
+
 @torch.library.custom_op(f"{_LIB}::sgd_momentum_", mutates_args=("param", "momentum_buf"))
 def sgd_momentum_(param: torch.Tensor, momentum_buf: torch.Tensor, grad: torch.Tensor, lr: float, momentum: float,
                   grad_scale: float = 1.0) -> None:
@@ -285,6 +355,34 @@ class Conv2dNHWC(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return torch.ops.cannet.conv2d_nhwc(x, self.weight, self.bias, self.dilation, self.relu)
+
+
+class BatchNorm2dNHWC(nn.Module):
+    """nn.BatchNorm2d(num_features) [+ ReLU] on NHWC 16-bit activations (``torch.ops.cannet.batch_norm_nhwc``).
+    Parameters and buffers carry nn.BatchNorm2d's names and shapes, so ``state_dict`` is interchangeable with it
+    (a ``make_layers(batch_norm=True)`` checkpoint loads).  The op is functional; in training this module updates the
+    running buffers from the op's stats under ATen's rule (unbiased variance, ``momentum=None``: cumulative average)."""
+
+    def __init__(self, num_features: int, eps: float = 1e-5, momentum: Optional[float] = 0.1, relu: bool = True):
+        super().__init__()
+        self.num_features, self.eps, self.momentum, self.relu = num_features, eps, momentum, relu
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+        self.register_buffer("running_mean", torch.zeros(num_features))
+        self.register_buffer("running_var", torch.ones(num_features))
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y, stats = torch.ops.cannet.batch_norm_nhwc(x, self.weight, self.bias, self.running_mean, self.running_var,
+                                                    self.training, self.eps, self.relu)
+        if self.training:
+            with torch.no_grad():
+                self.num_batches_tracked += 1
+                f = 1.0 / self.num_batches_tracked if self.momentum is None else self.momentum
+                m = x.numel() // x.shape[-1]
+                self.running_mean.lerp_(stats[0], f)
+                self.running_var.lerp_(stats[1] * (m / (m - 1)), f)
+        return y
 
 
 class ReluMaxPool2x2(nn.Module):
