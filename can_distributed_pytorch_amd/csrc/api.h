@@ -31,6 +31,17 @@ int can_conv_small_slices(long long M, int Ci, int Co);
 int can_conv_small_wgrad(const void* dy, const void* x, float* ws, long long ws_floats, float* dw, float* db, int N,
                          int H, int W, int Ci, int Co, int ksize, int dil, float beta, float scale, int dt,
                          void* stream);
+// Thin-channel convs (conv_thin.hip): exactly one of Ci, Co is 1 .. 8, the other a multiple of 16; ksize 1 / 3,
+// dil 1 .. 4, stride 1, 'same' padding.  can_conv_thin: thin Ci: w = [Co][K padded with zeros to whole MFMA steps
+// (conv_thin_plan.h thin_k_pad)], 16-bit y; thin Co: w = [Co][ksize^2 * Ci], y 16 bit or fp32 (f32out).  Either pack
+// is the forward or the flipped / transposed one.  can_conv_thin_wgrad: as can_conv_small_wgrad, with
+// can_conv_thin_partials(N * H * W, Ci, Co) partials in ws.
+int can_conv_thin(const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int Ci, int Co,
+                  int ksize, int dil, int epi, int f32out, int dt, void* stream);
+int can_conv_thin_partials(long long M, int Ci, int Co);
+int can_conv_thin_wgrad(const void* dy, const void* x, float* ws, long long ws_floats, float* dw, float* db, int N,
+                        int H, int W, int Ci, int Co, int ksize, int dil, float beta, float scale, int dt,
+                        void* stream);
 // stream events from one ring: record on a stream (returns the slot, < 0 error), wait for a slot, or both
 int can_event_record(void* stream);
 int can_event_wait(void* stream, int slot);

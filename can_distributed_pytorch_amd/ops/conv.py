@@ -507,6 +507,123 @@ def conv_small_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Op
                            float(beta) if c == 0 else 1.0, float(scale), dt_code(dy.dtype), _ext.stream_ptr(x.device))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Thin layers (csrc/conv_thin.hip): one channel count is 1 .. 8, the other a multiple of 16 (stems and heads)
+# ---------------------------------------------------------------------------------------------------------------------
+THIN_MAX = 8
+
+
+def thin_channels(ci: int, co: int) -> bool:
+    """Whether a ci -> co layer runs on the thin-channel kernels: exactly one side in 1 .. 8, the other a positive
+    multiple of 16."""
+    wide = lambda c: c >= 16 and c % 16 == 0  # noqa: E731
+    thin = lambda c: 1 <= c <= THIN_MAX  # noqa: E731
+    return (thin(ci) and wide(co)) or (thin(co) and wide(ci))
+
+
+def _check_thin(ci: int, co: int, ksize: int, dil: int):
+    if not thin_channels(ci, co):
+        raise ValueError(f"thin conv needs one channel count in 1 .. {THIN_MAX} and the other a multiple of 16, "
+                         f"got {ci} -> {co}")
+    if ksize not in (1, 3):
+        raise ValueError("ksize must be 1 or 3")
+    if not 1 <= dil <= SMALL_MAX_DIL:
+        raise ValueError(f"thin conv takes dilation 1 .. {SMALL_MAX_DIL}, got {dil}")
+
+
+def thin_k_pad(k: int) -> int:
+    """K of a thin-input layer padded to whole MFMA steps: 32 deep, a rest of 1 .. 16 one 16-deep step
+    (csrc/conv_thin_plan.h thin_k_pad)."""
+    return (k // 32) * 32 + 16 if 1 <= k % 32 <= 16 else -(-k // 32) * 32
+
+
+def pack_thin_in(wpack: torch.Tensor) -> torch.Tensor:
+    """A [Co][k^2 t] pack (pack_weight_fwd / pack_weight_dgrad) with zeros appended to thin_k_pad columns: what the
+    few -> many kernel loads as ready-made MFMA fragments."""
+    co, k = wpack.shape
+    out = torch.zeros(co, thin_k_pad(k), dtype=wpack.dtype, device=wpack.device)
+    out[:, :k] = wpack
+    return out
+
+
+def conv_thin(x: torch.Tensor, wpack: torch.Tensor, bias: Optional[torch.Tensor], *, ksize: int, dil: int = 1,
+              epi: int = EPI_BIAS_RELU, fp32_out: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_small for thin layers: y[N,H,W,Co] = epi(conv(x[N,H,W,Ci], W)), stride 1, 'same' padding, exactly one of
+    Ci / Co in 1 .. 8.  wpack = pack_weight_fwd (forward) or pack_weight_dgrad (data gradient, epi=EPI_NONE), [Co][k^2
+    Ci]; for a thin Ci it may already be pack_thin_in's padded form (it is padded here otherwise).  fp32_out: y in
+    fp32 instead of x.dtype, thin Co only."""
+    C = _ext.require()
+    if x.dim() != 4:
+        raise ValueError("x must be [N,H,W,C]")
+    n, h, w, ci = x.shape
+    _check_act(x, "x")
+    co, k = wpack.shape
+    dt = x.dtype
+    if wpack.dtype != dt or not wpack.is_contiguous():
+        raise ValueError(f"wpack must be contiguous {dt}")
+    _check_thin(ci, co, ksize, dil)
+    kk = ksize * ksize * ci
+    if ci <= THIN_MAX:
+        if fp32_out:
+            raise ValueError("fp32_out needs a thin Cout")
+        if k == kk and thin_k_pad(kk) != kk:
+            wpack = pack_thin_in(wpack)
+        elif k != thin_k_pad(kk):
+            raise ValueError(f"packed weight K={k} is neither {kk} nor its padded {thin_k_pad(kk)}")
+    elif k != kk:
+        raise ValueError(f"packed weight K={k} != {ksize}*{ksize}*{ci}")
+    if epi not in (EPI_BIAS_RELU, EPI_BIAS, EPI_NONE):
+        raise ValueError("thin conv takes EPI_BIAS_RELU, EPI_BIAS or EPI_NONE")
+    if epi != EPI_NONE:
+        if bias is None or bias.dtype != torch.float32 or bias.numel() != co or not bias.is_contiguous():
+            raise ValueError("bias must be contiguous fp32 [Cout]")
+    odt = torch.float32 if fp32_out else dt
+    if out is None:
+        out = torch.empty(n, h, w, co, dtype=odt, device=x.device)
+    elif tuple(out.shape) != (n, h, w, co) or out.dtype != odt or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous {odt} GPU tensor of shape {(n, h, w, co)}")
+    for i0, i1 in image_chunks(n, h * w * max(ci, co)):
+        C.conv_thin(x[i0:i1].data_ptr(), wpack.data_ptr(), bias.data_ptr() if epi != EPI_NONE else 0,
+                    out[i0:i1].data_ptr(), i1 - i0, h, w, ci, co, ksize, dil, epi, int(fp32_out), dt_code(dt),
+                    _ext.stream_ptr(x.device))
+    return out
+
+
+def conv_thin_ws_floats(m: int, ci: int, co: int, ksize: int) -> int:
+    """fp32 workspace of conv_thin_wgrad over m pixels: one dW + db partial per pixel slice and row half
+    (conv_thin_plan.h thin_wgrad_partials)."""
+    return _ext.require().conv_thin_partials(m, ci, co) * (co * ci * ksize * ksize + co)
+
+
+def conv_thin_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor], *, ksize: int,
+                    dil: int = 1, ws: Optional[WgradWorkspace] = None, beta: float = 0.0, scale: float = 1.0) -> None:
+    """conv_small_wgrad for thin layers: dw[Co,Ci,kh,kw] (fp32, PyTorch layout) = scale * sum_m dY[m,co] Xcol[m,k]
+    (+ beta * dw), db likewise; partials per pixel slice, summed in order."""
+    C = _ext.require()
+    _check_act(dy, "dy")
+    _check_act(x, "x", dtype=dy.dtype)
+    if x.dim() != 4 or dy.dim() != 4:
+        raise ValueError("dy / x must be [N,H,W,C]")
+    n, h, w, ci = x.shape
+    co = dy.shape[-1]
+    if tuple(dy.shape[:3]) != (n, h, w):
+        raise ValueError("dy/x spatial mismatch")
+    _check_thin(ci, co, ksize, dil)
+    if tuple(dw.shape) != (co, ci, ksize, ksize):
+        raise ValueError(f"dw shape {tuple(dw.shape)} != {(co, ci, ksize, ksize)}")
+    if dw.dtype != torch.float32 or not dw.is_contiguous():
+        raise ValueError("dw must be contiguous fp32")
+    if db is not None and (db.dtype != torch.float32 or db.numel() != co or not db.is_contiguous()):
+        raise ValueError("db must be contiguous fp32 [Co]")
+    ws = ws or WgradWorkspace(x.device)
+    # dW (and db) accumulate over image chunks: the first launch applies beta, the others add (beta = 1)
+    for c, (i0, i1) in enumerate(image_chunks(n, h * w * max(ci, co))):
+        buf = ws.reserve(conv_thin_ws_floats((i1 - i0) * h * w, ci, co, ksize))
+        C.conv_thin_wgrad(dy[i0:i1].data_ptr(), x[i0:i1].data_ptr(), buf.data_ptr(), buf.numel(), dw.data_ptr(),
+                          db.data_ptr() if db is not None else 0, i1 - i0, h, w, ci, co, ksize, dil,
+                          float(beta) if c == 0 else 1.0, float(scale), dt_code(dy.dtype), _ext.stream_ptr(x.device))
+
+
 def _ctx_wgrad_cus() -> int:
     """CUs the batched context 1x1 weight gradient is planned for.  It runs on the weight-gradient stream while the
     critical-path context backward (bilinear-transpose row / cell passes, ctx_bwd_final) runs on the compute stream;

@@ -17,6 +17,13 @@ GPU — and an autograd formula built from the native backward kernels.
       kernel with the flipped / transposed weight pack, the weight + bias gradients on the split-pixel weight-
       gradient kernels (fp32, deterministic slab reduction) — the reference's nn.Conv2d + ReLU
       (model/CANNet.py:14-17, 114-115) as one op.
+  cannet::conv2d_thin_nhwc(x, weight, bias, dilation, relu, fp32_out) -> y
+      the stem and the head of a network: conv2d_nhwc's contract for layers in which exactly one of Ci, Co is
+      1 .. 8 (the real count: an RGB image is [N,H,W,3], 6 bytes per pixel) and the other a multiple of 16; k = 1
+      or 3, dilation 1 .. 4.  fp32_out (thin Co only): y in fp32, for a density map that gets summed into a count.
+      Runs on csrc/conv_thin.hip: few -> many (stem forward, head data gradient) and many -> few (head forward,
+      stem data gradient) MFMA kernels, one weight-gradient kernel + deterministic slice reduce.  The data gradient
+      is computed only when x requires one.
   cannet::relu_max_pool2x2(x) -> (y, codes)
       the ReLU-fused 2x2 / stride-2 max-pool of an NHWC map: y = max_pool2d(relu(x), 2) (= relu of the window
       max); codes = int32 first-max one-hots (4 bits per channel, 0 where the window max is <= 0).  Backward
@@ -37,7 +44,8 @@ GPU — and an autograd formula built from the native backward kernels.
       (decoupled=True) on contiguous fp32 tensors, one kernel; ``step`` is the 1-based step of this call (the bias
       corrections are 1 - beta^step); no amsgrad, no maximize.
 
-``Conv2dNHWC`` / ``BatchNorm2dNHWC`` / ``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master parameters.
+``Conv2dNHWC`` / ``Conv2dThinNHWC`` / ``BatchNorm2dNHWC`` / ``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master
+parameters.
 """
 from __future__ import annotations
 
@@ -134,6 +142,98 @@ def _conv_bwd(ctx, dy):
 
 
 conv2d_nhwc.register_autograd(_conv_bwd, setup_context=_conv_setup)
+
+
+def _thin_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], dilation: int,
+                fp32_out: bool) -> Tuple[int, int, int]:
+    if x.dim() != 4:
+        raise ValueError("x must be NHWC [N,H,W,Ci]")
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3):
+        raise ValueError("weight must be [Co,Ci,k,k] with k = 1 or 3")
+    co, ci, k, _ = weight.shape
+    if x.shape[-1] != ci:
+        raise ValueError(f"x has {x.shape[-1]} channels, weight expects {ci}")
+    if not C.thin_channels(ci, co):
+        raise ValueError(f"cannet::conv2d_thin_nhwc needs exactly one of Ci, Co in 1 .. {C.THIN_MAX} and the other a "
+                         f"multiple of 16, got {ci} -> {co}")
+    if not 1 <= dilation <= C.SMALL_MAX_DIL:
+        raise ValueError(f"dilation must be 1 .. {C.SMALL_MAX_DIL}, got {dilation}")
+    if fp32_out and co > C.THIN_MAX:
+        raise ValueError("fp32_out needs a thin Co")
+    if x.dtype not in C.ACT_DTYPES:
+        raise ValueError(f"x must be bf16 or fp16, got {x.dtype}")
+    if weight.dtype != torch.float32:
+        raise ValueError("weight must be the fp32 master tensor")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != co):
+        raise ValueError("bias must be fp32 [Co]")
+    return ci, co, k
+
+
+@torch.library.custom_op(f"{_LIB}::conv2d_thin_nhwc", mutates_args=())
+def conv2d_thin_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], dilation: int = 1,
+                     relu: bool = True, fp32_out: bool = False) -> torch.Tensor:
+    ci, co, k = _thin_check(x, weight, bias, dilation, fp32_out)
+    x = x.contiguous()
+    wp = C.pack_weight_fwd(weight, x.dtype)
+    if bias is None:
+        if relu:
+            bias = torch.zeros(co, dtype=torch.float32, device=x.device)
+            epi = C.EPI_BIAS_RELU
+        else:
+            epi = C.EPI_NONE
+    else:
+        bias = bias.detach().contiguous()
+        epi = C.EPI_BIAS_RELU if relu else C.EPI_BIAS
+    return C.conv_thin(x, wp, bias, ksize=k, dil=dilation, epi=epi, fp32_out=fp32_out)
+
+
+@conv2d_thin_nhwc.register_fake
+def _(x, weight, bias, dilation=1, relu=True, fp32_out=False):
+    _thin_check(x, weight, bias, dilation, fp32_out)
+    return x.new_empty(*x.shape[:3], weight.shape[0], dtype=torch.float32 if fp32_out else x.dtype)
+
+
+@torch.library.custom_op(f"{_LIB}::conv2d_thin_nhwc_backward", mutates_args=())
+def conv2d_thin_nhwc_backward(dy: torch.Tensor, x: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, dilation: int,
+                              relu: bool, need_bias: bool,
+                              need_dx: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of conv2d_thin_nhwc; dx / dbias are empty tensors when need_dx / need_bias is False."""
+    co, ci, k, _ = weight.shape
+    dz = dy.to(x.dtype)
+    if relu:
+        dz = torch.where(y > 0, dz, torch.zeros((), dtype=dz.dtype, device=dz.device))
+    dz = dz.contiguous()
+    if need_dx:
+        dx = C.conv_thin(dz, C.pack_weight_dgrad(weight, x.dtype), None, ksize=k, dil=dilation, epi=C.EPI_NONE)
+    else:
+        dx = x.new_empty(0)
+    dw = torch.empty(co, ci, k, k, dtype=torch.float32, device=x.device)
+    db = torch.empty(co if need_bias else 0, dtype=torch.float32, device=x.device)
+    C.conv_thin_wgrad(dz, x.contiguous(), dw, db if need_bias else None, ksize=k, dil=dilation)
+    return dx, dw, db
+
+
+@conv2d_thin_nhwc_backward.register_fake
+def _(dy, x, y, weight, dilation, relu, need_bias, need_dx):
+    co = weight.shape[0]
+    return (x.new_empty(x.shape if need_dx else (0,)), weight.new_empty(weight.shape),
+            weight.new_empty(co if need_bias else 0))
+
+
+def _thin_setup(ctx, inputs, output):
+    x, weight, bias, dilation, relu, _ = inputs
+    ctx.save_for_backward(x, weight, output)
+    ctx.dilation, ctx.relu, ctx.has_bias = dilation, relu, bias is not None
+
+
+def _thin_bwd(ctx, dy):
+    x, weight, y = ctx.saved_tensors
+    need_dx = ctx.needs_input_grad[0]                    # an image normally needs no gradient
+    dx, dw, db = conv2d_thin_nhwc_backward(dy, x, y, weight, ctx.dilation, ctx.relu, ctx.has_bias, need_dx)
+    return (dx if need_dx else None), dw, (db if ctx.has_bias else None), None, None, None
+
+
+conv2d_thin_nhwc.register_autograd(_thin_bwd, setup_context=_thin_setup)
 
 
 @torch.library.custom_op(f"{_LIB}::relu_max_pool2x2", mutates_args=())
@@ -355,6 +455,29 @@ class Conv2dNHWC(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return torch.ops.cannet.conv2d_nhwc(x, self.weight, self.bias, self.dilation, self.relu)
+
+
+class Conv2dThinNHWC(nn.Module):
+    """Conv2dNHWC for a stem or a head (``torch.ops.cannet.conv2d_thin_nhwc``): exactly one of in_channels /
+    out_channels is 1 .. 8, the other a multiple of 16.  Parameters are fp32 in the PyTorch layout, so ``state_dict``
+    is interchangeable with nn.Conv2d's.  fp32_out (thin out_channels): the output is fp32."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: int = 3, dilation: int = 1,
+                 bias: bool = True, relu: bool = True, fp32_out: bool = False):
+        super().__init__()
+        if kernel_size not in (1, 3):
+            raise ValueError("kernel_size must be 1 or 3")
+        if not C.thin_channels(in_channels, out_channels):
+            raise ValueError("exactly one of in_channels / out_channels must be 1 .. 8, the other a multiple of 16")
+        if fp32_out and out_channels > C.THIN_MAX:
+            raise ValueError("fp32_out needs thin out_channels")
+        self.dilation, self.relu, self.fp32_out = dilation, relu, fp32_out
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+        self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
+        nn.init.normal_(self.weight, std=0.01)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return torch.ops.cannet.conv2d_thin_nhwc(x, self.weight, self.bias, self.dilation, self.relu, self.fp32_out)
 
 
 class BatchNorm2dNHWC(nn.Module):
