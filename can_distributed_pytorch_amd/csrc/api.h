@@ -124,6 +124,31 @@ int can_bn_forward(const void* x, void* y, const float* gamma, const float* beta
 int can_bn_backward(const void* dy, const void* x, const void* y, const float* gamma, const float* stats, double* part,
                     int S, float* fin, void* dx, long long M, int C, int training, int relu, int dt, void* stream);
 
+// resample.hip: adaptive average pool and bilinear resize of an NHWC 16-bit map [N][H][W][C] (C % 8 == 0) to
+// [N][oh][ow][C], forward and backward, fp32 arithmetic in a fixed order (plans: resample_plan.h).  Refused before any
+// launch: -2 C, -3 a size below 1, -5 an operand beyond the 32-bit indexing rule, -6 a form / staging / slice request
+// out of range (or a separable pool with more than 512 column bins) or a missing / short workspace, -7 a null operand,
+// -20 dt.
+// form: 0 planned, 1 direct, 2 separable (fp32 workspace rowacc [N][H][ow][C]); the plan query returns the form (> 0)
+// and the workspace size
+int can_pool_adaptive_plan(int N, int H, int W, int C, int oh, int ow, int form, long long* ws_floats);
+int can_pool_adaptive_fwd(const void* x, void* y, float* ws, long long ws_floats, int N, int H, int W, int C, int oh,
+                          int ow, int form, int dt, void* stream);
+// dy [N][oh][ow][C] -> dx [N][H][W][C]
+int can_pool_adaptive_bwd(const void* dy, void* dx, int N, int H, int W, int C, int oh, int ow, int dt, void* stream);
+// tv / th: the per-axis tap tables of ops/resample.py (int32 [5 L + 2 l]: i0, i1, lambda, w0, w1 per output, lo, hi
+// per source) on the device.  staged: -1 planned, 0 global reads, 1 LDS staging; out5 = (G, tile rows, strip width,
+// window rows, staged).  slices: 0 planned, 1 .. 64; out4 = (G, strip columns, column chunk, S), ws_floats = fp32
+// partials [S][N][h][w][C] when S > 1.
+int can_resize_bilinear_fwd_plan(int N, int h, int w, int C, int oh, int ow, int staged, int* out5);
+int can_resize_bilinear_bwd_plan(int N, int h, int w, int C, int oh, int ow, int slices, int* out4,
+                                 long long* ws_floats);
+int can_resize_bilinear_fwd(const void* x, void* y, const int* tv, const int* th, int N, int h, int w, int C, int oh,
+                            int ow, int staged, int dt, void* stream);
+// dy [N][oh][ow][C] -> dx [N][h][w][C]
+int can_resize_bilinear_bwd(const void* dy, void* dx, const int* tv, const int* th, float* ws, long long ws_floats,
+                            int N, int h, int w, int C, int oh, int ow, int slices, int dt, void* stream);
+
 // context.hip
 int can_ctx_reduce(int mode, const void* in0, const void* sdir, const void* dc, float* rowacc, float* cells, int N,
                    int h, int w, int C, int dt, void* stream, int wv);

@@ -35,6 +35,14 @@ GPU — and an autograd formula built from the native backward kernels.
       (running_mean, running_var).  Functional: the running buffers are never written; stats = fp32 [3, C] (mean,
       biased variance, rstd), not differentiable, is what the backward and ``BatchNorm2dNHWC``'s buffer update use.
       Backward: dz = dY masked by the stored y > 0, then dgamma / dbeta and dx on the native kernels.
+  cannet::adaptive_avg_pool_nhwc(x, oh, ow) -> y
+      F.adaptive_avg_pool2d of an NHWC bf16/fp16 map, C % 8 == 0, any sizes >= 1 (bins overlap when H % oh != 0,
+      oh > H is legal): fp32 sum of the bin / float(count), one rounding (csrc/resample.hip).  Backward: a gather
+      over the bins that hold each input pixel.
+  cannet::resize_bilinear_nhwc(x, oh, ow, align_corners) -> y
+      F.interpolate(x, (oh, ow), mode="bilinear", align_corners=...) of an NHWC bf16/fp16 map, C % 8 == 0, up or
+      down, any ratio; taps from float64 host tables, fma blends in fp32, one rounding.  Backward: the exact adjoint
+      as a gather (no atomics, fixed order).
   cannet::sgd_momentum_(param, momentum_buf, grad, lr, momentum, grad_scale) -> ()
       in-place fused SGD with momentum on contiguous fp32 tensors (torch.optim.SGD semantics, weight decay 0,
       dampening 0: buf = momentum * buf + grad_scale * grad; param -= lr * buf), one kernel.
@@ -45,7 +53,7 @@ GPU — and an autograd formula built from the native backward kernels.
       corrections are 1 - beta^step); no amsgrad, no maximize.
 
 ``Conv2dNHWC`` / ``Conv2dThinNHWC`` / ``BatchNorm2dNHWC`` / ``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master
-parameters.
+parameters; ``AdaptiveAvgPool2dNHWC`` / ``ResizeBilinearNHWC`` wrap the two resampling ops.
 """
 from __future__ import annotations
 
@@ -57,6 +65,7 @@ import torch.nn as nn
 from . import _ext
 from . import batchnorm as BN
 from . import conv as C
+from . import resample as RS
 
 _LIB = "cannet"
 
@@ -337,6 +346,85 @@ def _bn_bwd(ctx, dy, dstats):
 batch_norm_nhwc.register_autograd(_bn_bwd, setup_context=_bn_setup)
 
 
+def _resample_check(x: torch.Tensor, oh: int, ow: int) -> None:
+    if x.dim() != 4:
+        raise ValueError("x must be NHWC [N,H,W,C]")
+    if x.shape[-1] == 0 or x.shape[-1] % 8:
+        raise ValueError("the resampling ops need C a multiple of 8")
+    if x.dtype not in C.ACT_DTYPES:
+        raise ValueError(f"x must be bf16 or fp16, got {x.dtype}")
+    if min(*x.shape, oh, ow) < 1:
+        raise ValueError("every size must be >= 1")
+
+
+@torch.library.custom_op(f"{_LIB}::adaptive_avg_pool_nhwc", mutates_args=())
+def adaptive_avg_pool_nhwc(x: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
+    _resample_check(x, oh, ow)
+    return RS.adaptive_avg_pool(x.contiguous(), oh, ow)
+
+
+@adaptive_avg_pool_nhwc.register_fake
+def _(x, oh, ow):
+    _resample_check(x, oh, ow)
+    return x.new_empty(x.shape[0], oh, ow, x.shape[3])
+
+
+@torch.library.custom_op(f"{_LIB}::adaptive_avg_pool_nhwc_backward", mutates_args=())
+def adaptive_avg_pool_nhwc_backward(dy: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """dx [N,h,w,C] of adaptive_avg_pool_nhwc."""
+    return RS.adaptive_avg_pool_backward(dy.contiguous(), h, w)
+
+
+@adaptive_avg_pool_nhwc_backward.register_fake
+def _(dy, h, w):
+    return dy.new_empty(dy.shape[0], h, w, dy.shape[3])
+
+
+def _apool_setup(ctx, inputs, output):
+    ctx.hw = tuple(inputs[0].shape[1:3])
+
+
+def _apool_bwd(ctx, dy):
+    return adaptive_avg_pool_nhwc_backward(dy, *ctx.hw), None, None
+
+
+adaptive_avg_pool_nhwc.register_autograd(_apool_bwd, setup_context=_apool_setup)
+
+
+@torch.library.custom_op(f"{_LIB}::resize_bilinear_nhwc", mutates_args=())
+def resize_bilinear_nhwc(x: torch.Tensor, oh: int, ow: int, align_corners: bool = False) -> torch.Tensor:
+    _resample_check(x, oh, ow)
+    return RS.resize_bilinear(x.contiguous(), oh, ow, align_corners)
+
+
+@resize_bilinear_nhwc.register_fake
+def _(x, oh, ow, align_corners=False):
+    _resample_check(x, oh, ow)
+    return x.new_empty(x.shape[0], oh, ow, x.shape[3])
+
+
+@torch.library.custom_op(f"{_LIB}::resize_bilinear_nhwc_backward", mutates_args=())
+def resize_bilinear_nhwc_backward(dy: torch.Tensor, h: int, w: int, align_corners: bool) -> torch.Tensor:
+    """dx [N,h,w,C] of resize_bilinear_nhwc."""
+    return RS.resize_bilinear_backward(dy.contiguous(), h, w, align_corners)
+
+
+@resize_bilinear_nhwc_backward.register_fake
+def _(dy, h, w, align_corners):
+    return dy.new_empty(dy.shape[0], h, w, dy.shape[3])
+
+
+def _resize_setup(ctx, inputs, output):
+    ctx.hw, ctx.align_corners = tuple(inputs[0].shape[1:3]), inputs[3]
+
+
+def _resize_bwd(ctx, dy):
+    return resize_bilinear_nhwc_backward(dy, *ctx.hw, ctx.align_corners), None, None, None
+
+
+resize_bilinear_nhwc.register_autograd(_resize_bwd, setup_context=_resize_setup)
+
+
 @torch.library.custom_op(f"{_LIB}::sgd_momentum_", mutates_args=("param", "momentum_buf"))
 def sgd_momentum_(param: torch.Tensor, momentum_buf: torch.Tensor, grad: torch.Tensor, lr: float, momentum: float,
                   grad_scale: float = 1.0) -> None:
@@ -514,3 +602,47 @@ class ReluMaxPool2x2(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return torch.ops.cannet.relu_max_pool2x2(x)[0]
+
+
+def _pair(v) -> Tuple[int, int]:
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+class AdaptiveAvgPool2dNHWC(nn.Module):
+    """nn.AdaptiveAvgPool2d(output_size) on NHWC 16-bit activations (``torch.ops.cannet.adaptive_avg_pool_nhwc``);
+    output_size is an int or a pair."""
+
+    def __init__(self, output_size):
+        super().__init__()
+        self.output_size = _pair(output_size)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return torch.ops.cannet.adaptive_avg_pool_nhwc(x, *self.output_size)
+
+
+class ResizeBilinearNHWC(nn.Module):
+    """nn.Upsample(size, scale_factor, mode="bilinear", align_corners=...) on NHWC 16-bit activations
+    (``torch.ops.cannet.resize_bilinear_nhwc``).  Exactly one of size (int or pair) and scale_factor (number or pair)
+    is given; with scale_factor the output size is F.interpolate's floor(input size * scale_factor), and the taps are
+    those of that size (``recompute_scale_factor=True`` where the two differ, i.e. for fractional factors)."""
+
+    def __init__(self, size=None, scale_factor=None, align_corners: bool = False):
+        super().__init__()
+        if (size is None) == (scale_factor is None):
+            raise ValueError("exactly one of size and scale_factor must be given")
+        self.size = None if size is None else _pair(size)
+        if scale_factor is None:
+            self.scale_factor = None
+        else:
+            sf = (scale_factor, scale_factor) if isinstance(scale_factor, (int, float)) else tuple(scale_factor)
+            self.scale_factor = (float(sf[0]), float(sf[1]))
+        self.align_corners = bool(align_corners)
+
+    def output_size(self, h: int, w: int) -> Tuple[int, int]:
+        if self.size is not None:
+            return self.size
+        return int(float(h) * self.scale_factor[0]), int(float(w) * self.scale_factor[1])
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        oh, ow = self.output_size(x.shape[1], x.shape[2])
+        return torch.ops.cannet.resize_bilinear_nhwc(x, oh, ow, self.align_corners)
