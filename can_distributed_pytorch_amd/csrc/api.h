@@ -21,7 +21,7 @@ int can_conv_wgrad(const void* dy, const void* x, float* ws, long long ws_floats
                    int W, int Cin, int Cout, int ksize, int dil, int first, float beta, float scale,
                    const float* dscale, int dt, void* stream, const float* bext, int bext_rows);
 // Small-channel convs (conv_small.hip): Ci, Co multiples of 16, ksize 1 / 3, dil 1 .. 4 (-41 beyond), stride 1, 'same'
-// padding.  can_conv_small: epi EPI_BIAS_RELU / EPI_BIAS / EPI_NONE, w the K-contiguous pack [Co][ksize^2 * Ci]
+// padding (ksize 5 / 7: conv_large.hip, below). can_conv_small: epi EPI_BIAS_RELU / EPI_BIAS / EPI_NONE, w the K-contiguous pack [Co][ksize^2 * Ci]
 // (forward) or the flipped / transposed one (data gradient).  can_conv_small_wgrad: dw [Co][Ci][k][k] and db [Co]
 // (optional) = scale * sum (+ beta * old); ws holds can_conv_small_slices(N * H * W, Ci, Co) partials of
 // Co * Ci * ksize^2 + Co floats each (-43 when ws_floats is less).
@@ -29,6 +29,14 @@ int can_conv_small(const void* x, const void* w, const float* bias, void* y, int
                    int ksize, int dil, int epi, int dt, void* stream);
 int can_conv_small_slices(long long M, int Ci, int Co);
 int can_conv_small_wgrad(const void* dy, const void* x, float* ws, long long ws_floats, float* dw, float* db, int N,
+                         int H, int W, int Ci, int Co, int ksize, int dil, float beta, float scale, int dt,
+                         void* stream);
+// Large-kernel convs (conv_large.hip): ksize 5 / 7 with dil * (ksize / 2) <= 4 (-41 beyond), any Ci, Co multiples of 16;
+// otherwise the contract of can_conv_small / can_conv_small_wgrad (same packs, epilogues, slices and workspace), which
+// hand every ksize > 3 to these.
+int can_conv_large(const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int Ci, int Co,
+                   int ksize, int dil, int epi, int dt, void* stream);
+int can_conv_large_wgrad(const void* dy, const void* x, float* ws, long long ws_floats, float* dw, float* db, int N,
                          int H, int W, int Ci, int Co, int ksize, int dil, float beta, float scale, int dt,
                          void* stream);
 // Thin-channel convs (conv_thin.hip): exactly one of Ci, Co is 1 .. 8, the other a multiple of 16; ksize 1 / 3,

@@ -34,7 +34,7 @@
 // odd block keeps the identity order and stores 8 B.  Epilogue: fp32 + bias, optional ReLU, one RNE to 16 bits;
 // ragged tiles are masked at the store.
 //
-// wgrad_c16_kernel<DT, KS> + c16_reduce_kernel: dW [Co][Ci][k][k] and db [Co] in fp32
+// wgrad_c16_kernel<DT, KS> + c16_reduce_kernel (conv_small_reduce.h): dW [Co][Ci][k][k] and db [Co] in fp32
 // ------------------------------------------------------------------------------------------------------
 // The GEMM reduces over pixels.  A block owns all KS^2 taps of a 32 x 32 (co x ci) block of dW and a slice of the
 // pixel tiles: grid = (channel blocks, slices).  Wave (sco, sci) owns the 16 x 16 sub-block and all taps (9 f32x4).
@@ -54,6 +54,7 @@
 #include "conv_epilogue.h"
 #include "conv_small_plan.h"
 #include "conv_small_dev.h"
+#include "conv_small_reduce.h"
 
 namespace can {
 namespace {
@@ -324,20 +325,6 @@ __global__ void __launch_bounds__(256) wgrad_c16_kernel(C16WgArgs a) {
   }
 }
 
-// out[i] = scale * (part_0[i] + part_1[i] + ...) (+ beta * out[i]): slices in slice order; i < plane -> dw, else db
-__global__ void __launch_bounds__(256) c16_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                         float* __restrict__ db, int S, int plane, int Co, float beta,
-                                                         float scale) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int n = plane + (db != nullptr ? Co : 0);
-  if (i >= n) return;
-  const size_t stride = (size_t)plane + Co;
-  float s = 0.f;
-  for (int sl = 0; sl < S; ++sl) s += ws[(size_t)sl * stride + i];
-  float* out = i < plane ? dw + i : db + (i - plane);
-  *out = (beta != 0.f) ? scale * s + beta * *out : scale * s;
-}
-
 size_t c16_fwd_lds(int ksize, int dil, int nj) {
   const int d = dil * (ksize / 2);
   return (size_t)((c16_halo_pixels(d) * C16_FWD_PITCH + 15) & ~15) + (size_t)ksize * ksize * nj * 1024;
@@ -406,6 +393,7 @@ int c16_check(int N, int H, int W, int Ci, int Co, int ksize, int dil) {
 extern "C" int can_conv_small(const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int Ci,
                               int Co, int ksize, int dil, int epi, int dt, void* stream) {
   using namespace can;
+  if (ksize > 3) return can_conv_large(x, w, bias, y, N, H, W, Ci, Co, ksize, dil, epi, dt, stream);   // conv_large.hip
   const int rc = c16_check(N, H, W, Ci, Co, ksize, dil);
   if (rc) return rc;
   if (epi != EPI_BIAS_RELU && epi != EPI_BIAS && epi != EPI_NONE) return C16_ERR_SHAPE;
@@ -425,6 +413,8 @@ extern "C" int can_conv_small_wgrad(const void* dy, const void* x, float* ws, lo
                                     int N, int H, int W, int Ci, int Co, int ksize, int dil, float beta, float scale,
                                     int dt, void* stream) {
   using namespace can;
+  if (ksize > 3)
+    return can_conv_large_wgrad(dy, x, ws, ws_floats, dw, db, N, H, W, Ci, Co, ksize, dil, beta, scale, dt, stream);
   const int rc = c16_check(N, H, W, Ci, Co, ksize, dil);
   if (rc) return rc;
   const int S = c16_wgrad_slices((long long)N * H * W, Ci, Co, can_device_cus());
@@ -441,8 +431,5 @@ extern "C" int can_conv_small_wgrad(const void* dy, const void* x, float* ws, lo
   if (dt == DT_F16) lrc = launch_wg_ks<DT_F16>(a, ksize, S, s);
   else if (dt == DT_BF16) lrc = launch_wg_ks<DT_BF16>(a, ksize, S, s);
   if (lrc) return lrc;
-  const int plane = Co * Ci * ksize * ksize;
-  const int n = plane + (db != nullptr ? Co : 0);
-  hipLaunchKernelGGL(c16_reduce_kernel, dim3(c16_cdiv(n, 256)), dim3(256), 0, s, ws, dw, db, S, plane, Co, beta, scale);
-  return (int)hipGetLastError();
+  return c16_reduce(ws, dw, db, S, Co * Ci * ksize * ksize, Co, beta, scale, s);
 }

@@ -1,5 +1,5 @@
 // Device helpers of the small-channel conv kernels (conv_small.hip), shared with the thin-channel family
-// (conv_thin.hip): the 16-deep MFMA, halo staging through registers, and the transposing LDS fragment read.  Each translation unit gets its own copy (anonymous namespace).
+// (conv_thin.hip) and the large-kernel family (conv_large.hip): the 16-deep MFMA, halo staging through registers, and the transposing LDS fragment read.  Each translation unit gets its own copy (anonymous namespace).
 #pragma once
 #include "common.h"
 #include "conv_small_plan.h"

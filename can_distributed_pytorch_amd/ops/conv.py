@@ -419,9 +419,11 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Small-channel layers (csrc/conv_small.hip): Ci, Co multiples of 16, not both multiples of 64
+# Small-channel layers (csrc/conv_small.hip): Ci, Co multiples of 16, not both multiples of 64; and, through the same
+# two functions with ksize 5 / 7, the large-kernel layers (csrc/conv_large.hip): any Ci, Co multiples of 16
 # ---------------------------------------------------------------------------------------------------------------------
 SMALL_MAX_DIL = 4
+LARGE_MAX_REACH = 4      # 5x5 / 7x7 layers (csrc/conv_large.hip): dilation * (ksize // 2) pixels of halo at most
 
 
 def small_channels(ci: int, co: int) -> bool:
@@ -432,10 +434,13 @@ def small_channels(ci: int, co: int) -> bool:
 def _check_small(ci: int, co: int, ksize: int, dil: int):
     if ci % 16 or co % 16 or ci < 16 or co < 16:
         raise ValueError(f"small-channel conv needs Cin / Cout multiples of 16, got {ci} -> {co}")
-    if ksize not in (1, 3):
-        raise ValueError("ksize must be 1 or 3")
+    if ksize not in (1, 3, 5, 7):
+        raise ValueError("ksize must be 1, 3, 5 or 7")
     if not 1 <= dil <= SMALL_MAX_DIL:
         raise ValueError(f"small-channel conv takes dilation 1 .. {SMALL_MAX_DIL}, got {dil}")
+    if ksize > 3 and dil * (ksize // 2) > LARGE_MAX_REACH:
+        raise ValueError(f"a {ksize}x{ksize} conv takes dilation * {ksize // 2} <= {LARGE_MAX_REACH}, got "
+                         f"dilation {dil}")
 
 
 def conv_small(x: torch.Tensor, wpack: torch.Tensor, bias: Optional[torch.Tensor], *, ksize: int, dil: int = 1,

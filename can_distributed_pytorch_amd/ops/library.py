@@ -6,8 +6,11 @@ shape propagation — so ``torch.compile`` traces them without graph breaks and 
 GPU — and an autograd formula built from the native backward kernels.
 
   cannet::conv2d_nhwc(x, weight, bias, dilation, relu) -> y
-      x [N,H,W,Ci] bf16/fp16 (NHWC, contiguous), weight [Co,Ci,k,k] fp32 master (k = 1 or 3), bias [Co] fp32 or
-      None; stride 1, 'same' padding dilation*(k//2); y = [relu](conv(x, weight) + bias) in x.dtype.
+      x [N,H,W,Ci] bf16/fp16 (NHWC, contiguous), weight [Co,Ci,k,k] fp32 master (k = 1, 3, 5 or 7), bias [Co] fp32
+      or None; stride 1, 'same' padding dilation*(k//2); y = [relu](conv(x, weight) + bias) in x.dtype.
+      k = 5 (dilation 1 - 2) and k = 7 (dilation 1), the layers of multi-column and scale-aggregation networks, run
+      on the streamed-weight kernels of csrc/conv_large.hip whatever the channel multiples (``conv_small`` /
+      ``conv_small_wgrad`` with ksize 5 / 7); the rest of this entry is about k = 1 and 3.
       Ci, Co multiples of 16 (the first 3-channel layer has its own kernel inside the executor).  When both are
       multiples of 64 the op runs on the 64-channel-chunk kernels described next; otherwise (a 32-, 48- or 96-channel
       stage, a 1x1 bottleneck to 16 channels, a 160-channel trunk ...) forward, data gradient and weight gradient run
@@ -70,12 +73,15 @@ from . import resample as RS
 _LIB = "cannet"
 
 
-def _conv_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> Tuple[int, int, int]:
+def _conv_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                dilation: int) -> Tuple[int, int, int]:
     if x.dim() != 4:
         raise ValueError("x must be NHWC [N,H,W,Ci]")
-    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3):
-        raise ValueError("weight must be [Co,Ci,k,k] with k = 1 or 3")
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3, 5, 7):
+        raise ValueError("weight must be [Co,Ci,k,k] with k = 1, 3, 5 or 7")
     co, ci, k, _ = weight.shape
+    if k > 3 and not 1 <= dilation * (k // 2) <= C.LARGE_MAX_REACH:
+        raise ValueError(f"a {k}x{k} layer needs dilation * {k // 2} <= {C.LARGE_MAX_REACH}, got dilation {dilation}")
     if x.shape[-1] != ci:
         raise ValueError(f"x has {x.shape[-1]} channels, weight expects {ci}")
     if ci % 16 or co % 16 or ci == 0 or co == 0:
@@ -92,7 +98,7 @@ def _conv_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
 @torch.library.custom_op(f"{_LIB}::conv2d_nhwc", mutates_args=())
 def conv2d_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], dilation: int = 1,
                 relu: bool = True) -> torch.Tensor:
-    ci, co, k = _conv_check(x, weight, bias)
+    ci, co, k = _conv_check(x, weight, bias, dilation)
     x = x.contiguous()
     wp = C.pack_weight_fwd(weight, x.dtype)
     if bias is None:
@@ -104,14 +110,14 @@ def conv2d_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     else:
         bias = bias.detach().contiguous()
         epi = C.EPI_BIAS_RELU if relu else C.EPI_BIAS
-    if C.small_channels(ci, co):
+    if k > 3 or C.small_channels(ci, co):
         return C.conv_small(x, wp, bias, ksize=k, dil=dilation, epi=epi)
     return C.conv_igemm(x, wp, bias, ksize=k, dil=dilation, epi=epi)
 
 
 @conv2d_nhwc.register_fake
 def _(x, weight, bias, dilation=1, relu=True):
-    _conv_check(x, weight, bias)
+    _conv_check(x, weight, bias, dilation)
     return x.new_empty(*x.shape[:3], weight.shape[0])
 
 
@@ -124,7 +130,8 @@ def conv2d_nhwc_backward(dy: torch.Tensor, x: torch.Tensor, y: torch.Tensor, wei
     if relu:
         dz = torch.where(y > 0, dz, torch.zeros((), dtype=dz.dtype, device=dz.device))
     dz = dz.contiguous()
-    conv, wgrad = (C.conv_small, C.conv_small_wgrad) if C.small_channels(ci, co) else (C.conv_igemm, C.conv_wgrad)
+    small = k > 3 or C.small_channels(ci, co)
+    conv, wgrad = (C.conv_small, C.conv_small_wgrad) if small else (C.conv_igemm, C.conv_wgrad)
     dx = conv(dz, C.pack_weight_dgrad(weight, x.dtype), None, ksize=k, dil=dilation, epi=C.EPI_NONE)
     dw = torch.empty(co, ci, k, k, dtype=torch.float32, device=x.device)
     db = torch.empty(co if need_bias else 0, dtype=torch.float32, device=x.device)
@@ -534,8 +541,8 @@ class Conv2dNHWC(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int = 3, dilation: int = 1,
                  bias: bool = True, relu: bool = True):
         super().__init__()
-        if kernel_size not in (1, 3):
-            raise ValueError("kernel_size must be 1 or 3")
+        if kernel_size not in (1, 3, 5, 7):
+            raise ValueError("kernel_size must be 1, 3, 5 or 7")
         self.dilation, self.relu = dilation, relu
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
