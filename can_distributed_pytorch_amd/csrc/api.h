@@ -39,6 +39,23 @@ int can_conv_large(const void* x, const void* w, const float* bias, void* y, int
 int can_conv_large_wgrad(const void* dy, const void* x, float* ws, long long ws_floats, float* dw, float* db, int N,
                          int H, int W, int Ci, int Co, int ksize, int dil, float beta, float scale, int dt,
                          void* stream);
+// Stride-2 convs (conv_stride2.hip): ksize 1 .. 4, padding (ksize - 1) / 2, Ci and Co multiples of 16, the large map
+// even in H and W, the small map H/2 x W/2.  Refused before any launch: -50 a shape (odd or empty map, channels, epi),
+// -51 ksize, -52 an operand beyond the 32-bit indexing, -53 a short workspace.
+// can_conv_down2: y [N][H/2][W/2][Co] = epi(conv(x [N][H][W][Ci], stride 2)), w = [Co][ksize^2 * Ci].
+// can_conv_up2: y [N][2 h][2 w][Co] = epi(transposed conv(x [N][h][w][Ci], stride 2)), w = [Co][ksize^2 * Ci], not flipped.
+// Each is the other's data gradient.  can_conv_s2_wgrad: dw [Ca][Cb][k][k] = scale * sum small[.., a] big[.., b]
+// (+ beta * old) over small [N][h][w][Ca] and big [N][2 h][2 w][Cb]; db (optional) the pixel sum of the small
+// (bias_of 1, [Ca]) or the large map (bias_of 2, [Cb]); ws holds can_conv_s2_slices(N * h * w, Ca, Cb) partials of
+// Ca * Cb * ksize^2 + (Ca or Cb, db's length) floats each.
+int can_conv_down2(const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int Ci, int Co,
+                   int ksize, int epi, int dt, void* stream);
+int can_conv_up2(const void* x, const void* w, const float* bias, void* y, int N, int h, int w_, int Ci, int Co,
+                 int ksize, int epi, int dt, void* stream);
+int can_conv_s2_slices(long long M, int Ca, int Cb);
+int can_conv_s2_wgrad(const void* small, const void* big, float* ws, long long ws_floats, float* dw, float* db, int N,
+                      int h, int w_, int Ca, int Cb, int ksize, int bias_of, float beta, float scale, int dt,
+                      void* stream);
 // Thin-channel convs (conv_thin.hip): exactly one of Ci, Co is 1 .. 8, the other a multiple of 16; ksize 1 / 3,
 // dil 1 .. 4, stride 1, 'same' padding.  can_conv_thin: thin Ci: w = [Co][K padded with zeros to whole MFMA steps
 // (conv_thin_plan.h thin_k_pad)], 16-bit y; thin Co: w = [Co][ksize^2 * Ci], y 16 bit or fp32 (f32out).  Either pack

@@ -513,6 +513,124 @@ def conv_small_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Op
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Stride-2 layers (csrc/conv_stride2.hip): the down-sampling conv and the 2x transposed conv, each the other's data
+# gradient; Ci, Co multiples of 16, ksize 1 .. 4, padding (ksize - 1) // 2, a large map of even H x W and a small map of
+# H/2 x W/2
+# ---------------------------------------------------------------------------------------------------------------------
+S2_MAX_K = 4
+_S2_BIAS_OF = {"small": 1, "big": 2}
+
+
+def pack_weight_up(wt: torch.Tensor, dtype: torch.dtype = BF16) -> torch.Tensor:
+    """A transposed conv's weight [Cin][Cout][kh][kw] (nn.ConvTranspose2d's layout) -> [Cout][kh][kw][Cin], not
+    flipped: what conv_up2 reads.  A down-sampling layer's weight [Co][Ci][k][k] IS the weight of its data gradient
+    in this layout (the transposed conv from Co to Ci channels)."""
+    co = wt.shape[1]
+    return wt.detach().permute(1, 2, 3, 0).reshape(co, -1).to(dtype).contiguous()
+
+
+def _check_s2(ci: int, co: int, ksize: int, big_h: int, big_w: int):
+    if ci % 16 or co % 16 or ci < 16 or co < 16:
+        raise ValueError(f"stride-2 conv needs Cin / Cout multiples of 16, got {ci} -> {co}")
+    if not 1 <= ksize <= S2_MAX_K:
+        raise ValueError(f"stride-2 conv takes ksize 1 .. {S2_MAX_K}, got {ksize}")
+    if big_h % 2 or big_w % 2 or big_h < 2 or big_w < 2:
+        raise ValueError(f"stride-2 conv needs a large map of even H and W, got {big_h} x {big_w}")
+
+
+def _s2_data(entry: str, x: torch.Tensor, wpack: torch.Tensor, bias: Optional[torch.Tensor], ksize: int, epi: int,
+             out: Optional[torch.Tensor], up: bool) -> torch.Tensor:
+    C = _ext.require()
+    if x.dim() != 4:
+        raise ValueError("x must be [N,H,W,C]")
+    n, h, w, ci = x.shape
+    _check_act(x, "x")
+    co, k = wpack.shape
+    dt = x.dtype
+    if wpack.dtype != dt or not wpack.is_contiguous():
+        raise ValueError(f"wpack must be contiguous {dt}")
+    bh, bw = (2 * h, 2 * w) if up else (h, w)            # the large map
+    _check_s2(ci, co, ksize, bh, bw)
+    if k != ksize * ksize * ci:
+        raise ValueError(f"packed weight K={k} != {ksize}*{ksize}*{ci}")
+    if epi not in (EPI_BIAS_RELU, EPI_BIAS, EPI_NONE):
+        raise ValueError("stride-2 conv takes EPI_BIAS_RELU, EPI_BIAS or EPI_NONE")
+    if epi != EPI_NONE:
+        if bias is None or bias.dtype != torch.float32 or bias.numel() != co or not bias.is_contiguous():
+            raise ValueError("bias must be contiguous fp32 [Cout]")
+    oshape = (n, 2 * h, 2 * w, co) if up else (n, h // 2, w // 2, co)
+    if out is None:
+        out = torch.empty(*oshape, dtype=dt, device=x.device)
+    else:
+        if tuple(out.shape) != oshape:
+            raise ValueError("out has the wrong shape")
+        _check_act(out, "out", dtype=dt)
+    launch = getattr(C, entry)
+    for i0, i1 in image_chunks(n, bh * bw * max(ci, co)):           # the large map governs the chunk
+        launch(x[i0:i1].data_ptr(), wpack.data_ptr(), bias.data_ptr() if epi != EPI_NONE else 0,
+               out[i0:i1].data_ptr(), i1 - i0, h, w, ci, co, ksize, epi, dt_code(dt), _ext.stream_ptr(x.device))
+    return out
+
+
+def conv_down2(x: torch.Tensor, wpack: torch.Tensor, bias: Optional[torch.Tensor], *, ksize: int,
+               epi: int = EPI_BIAS_RELU, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[N,H/2,W/2,Co] = epi(conv(x[N,H,W,Ci], W, stride 2, padding (ksize - 1) // 2)), H and W even;
+    wpack = pack_weight_fwd(w [Co,Ci,k,k]).  With pack_weight_fwd(wt [Ci',Co',k,k]) of a transposed conv's weight and
+    epi=EPI_NONE it is that layer's data gradient."""
+    return _s2_data("conv_down2", x, wpack, bias, ksize, epi, out, False)
+
+
+def conv_up2(x: torch.Tensor, wpack: torch.Tensor, bias: Optional[torch.Tensor], *, ksize: int,
+             epi: int = EPI_BIAS_RELU, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[N,2h,2w,Co] = epi(conv_transpose(x[N,h,w,Ci], Wt, stride 2, padding (ksize - 1) // 2, output_padding
+    ksize % 2)); wpack = pack_weight_up(wt [Ci,Co,k,k]).  With pack_weight_up(w [Co',Ci',k,k]) of a down-sampling
+    layer's weight and epi=EPI_NONE it is that layer's data gradient."""
+    return _s2_data("conv_up2", x, wpack, bias, ksize, epi, out, True)
+
+
+def conv_s2_ws_floats(m: int, ca: int, cb: int, ksize: int) -> int:
+    """fp32 workspace of conv_s2_wgrad over m small-map pixels: one dW + db partial per pixel slice, db over either
+    operand's channels."""
+    return _ext.require().conv_s2_slices(m, ca, cb) * (ca * cb * ksize * ksize + max(ca, cb))
+
+
+def conv_s2_wgrad(small: torch.Tensor, big: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor], *, ksize: int,
+                  bias_of: str = "small", ws: Optional[WgradWorkspace] = None, beta: float = 0.0,
+                  scale: float = 1.0) -> None:
+    """The weight gradient of both stride-2 layers: dw[Ca,Cb,kh,kw] (fp32) = scale * sum small[n,i,j,a] *
+    big[n,2i-p+kh,2j-p+kw,b] (+ beta * dw) over small [N,h,w,Ca] and big [N,2h,2w,Cb].  Down: small = dY, big = x ->
+    [Co,Ci,k,k], bias_of="small"; up: small = x, big = dY -> [Ci,Co,k,k], bias_of="big".  db = the pixel sum of the
+    operand bias_of names, likewise scaled; partials per pixel slice of the small map, summed in slice order."""
+    C = _ext.require()
+    _check_act(small, "small")
+    _check_act(big, "big", dtype=small.dtype)
+    if small.dim() != 4 or big.dim() != 4:
+        raise ValueError("small / big must be [N,H,W,C]")
+    if bias_of not in _S2_BIAS_OF:
+        raise ValueError('bias_of must be "small" or "big"')
+    n, h, w, ca = small.shape
+    cb = big.shape[-1]
+    if tuple(big.shape[:3]) != (n, 2 * h, 2 * w):
+        raise ValueError("big must be [N,2h,2w,Cb] for small [N,h,w,Ca]")
+    _check_s2(ca, cb, ksize, 2 * h, 2 * w)
+    if tuple(dw.shape) != (ca, cb, ksize, ksize):
+        raise ValueError(f"dw shape {tuple(dw.shape)} != {(ca, cb, ksize, ksize)}")
+    if dw.dtype != torch.float32 or not dw.is_contiguous():
+        raise ValueError("dw must be contiguous fp32")
+    cdb = ca if bias_of == "small" else cb
+    if db is not None and (db.dtype != torch.float32 or db.numel() != cdb or not db.is_contiguous()):
+        raise ValueError(f"db must be contiguous fp32 [{cdb}]")
+    ws = ws or WgradWorkspace(small.device)
+    # dW (and db) accumulate over image chunks: the first launch applies beta, the others add (beta = 1)
+    for c, (i0, i1) in enumerate(image_chunks(n, 4 * h * w * max(ca, cb))):
+        buf = ws.reserve(conv_s2_ws_floats((i1 - i0) * h * w, ca, cb, ksize))
+        C.conv_s2_wgrad(small[i0:i1].data_ptr(), big[i0:i1].data_ptr(), buf.data_ptr(), buf.numel(), dw.data_ptr(),
+                        db.data_ptr() if db is not None else 0, i1 - i0, h, w, ca, cb, ksize, _S2_BIAS_OF[bias_of],
+                        float(beta) if c == 0 else 1.0, float(scale), dt_code(small.dtype),
+                        _ext.stream_ptr(small.device))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Thin layers (csrc/conv_thin.hip): one channel count is 1 .. 8, the other a multiple of 16 (stems and heads)
 # ---------------------------------------------------------------------------------------------------------------------
 THIN_MAX = 8

@@ -27,6 +27,20 @@ GPU — and an autograd formula built from the native backward kernels.
       Runs on csrc/conv_thin.hip: few -> many (stem forward, head data gradient) and many -> few (head forward,
       stem data gradient) MFMA kernels, one weight-gradient kernel + deterministic slice reduce.  The data gradient
       is computed only when x requires one.
+  cannet::conv2d_down2_nhwc(x, weight, bias, relu) -> y
+      the learned down-sampling of a backbone: F.conv2d(x, weight, bias, stride=2, padding=(k - 1) // 2) [+ ReLU], x
+      [N,H,W,Ci] with H and W even, weight [Co,Ci,k,k] fp32, k = 1 .. 4, Ci and Co any multiples of 16, y
+      [N,H/2,W/2,Co].  Runs on csrc/conv_stride2.hip: a stride-2 gather out of a window staged split by column
+      parity.  Backward: dY masked by y > 0, the data gradient as the transposed conv below (``conv_up2`` on
+      ``pack_weight_up(weight)``), the weight + bias gradients on the stride-2 weight-gradient kernel
+      (``conv_s2_wgrad``, deterministic slice reduction).
+  cannet::conv_transpose2d_up2_nhwc(x, weight, bias, relu) -> y
+      the learned 2x up-sampling of a decoder: F.conv_transpose2d(x, weight, bias, stride=2, padding=(k - 1) // 2,
+      output_padding=k % 2) [+ ReLU], x [N,h,w,Ci], weight [Ci,Co,k,k] fp32 (nn.ConvTranspose2d's layout), k = 1 .. 4,
+      y [N,2h,2w,Co].  Same unit: the four output parity classes as stride-1 convs of the small map over the taps
+      that reach them, no scatter and no inserted zeros.  Backward: the data gradient is the down-sampling conv
+      (``conv_down2`` on ``pack_weight_fwd(weight)``), the weight gradient the same kernel with the operands' roles
+      swapped, which yields [Ci,Co,k,k] directly.
   cannet::relu_max_pool2x2(x) -> (y, codes)
       the ReLU-fused 2x2 / stride-2 max-pool of an NHWC map: y = max_pool2d(relu(x), 2) (= relu of the window
       max); codes = int32 first-max one-hots (4 bits per channel, 0 where the window max is <= 0).  Backward
@@ -55,8 +69,8 @@ GPU — and an autograd formula built from the native backward kernels.
       (decoupled=True) on contiguous fp32 tensors, one kernel; ``step`` is the 1-based step of this call (the bias
       corrections are 1 - beta^step); no amsgrad, no maximize.
 
-``Conv2dNHWC`` / ``Conv2dThinNHWC`` / ``BatchNorm2dNHWC`` / ``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master
-parameters; ``AdaptiveAvgPool2dNHWC`` / ``ResizeBilinearNHWC`` wrap the two resampling ops.
+``Conv2dNHWC`` / ``Conv2dThinNHWC`` / ``Conv2dDown2NHWC`` / ``ConvTranspose2dUp2NHWC`` / ``BatchNorm2dNHWC`` /
+``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master parameters; ``AdaptiveAvgPool2dNHWC`` / ``ResizeBilinearNHWC`` wrap the two resampling ops.
 """
 from __future__ import annotations
 
@@ -250,6 +264,137 @@ def _thin_bwd(ctx, dy):
 
 
 conv2d_thin_nhwc.register_autograd(_thin_bwd, setup_context=_thin_setup)
+
+
+def _s2_check(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], up: bool) -> Tuple[int, int, int]:
+    """(ci, co, k) of a stride-2 layer; weight [Co,Ci,k,k] (down) or [Ci,Co,k,k] (up, nn.ConvTranspose2d's layout)."""
+    name = "cannet::conv_transpose2d_up2_nhwc" if up else "cannet::conv2d_down2_nhwc"
+    if x.dim() != 4:
+        raise ValueError("x must be NHWC [N,H,W,Ci]")
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or not 1 <= weight.shape[2] <= C.S2_MAX_K:
+        raise ValueError(f"weight must be 4-d with k x k taps, k = 1 .. {C.S2_MAX_K}")
+    k = weight.shape[2]
+    ci, co = (weight.shape[0], weight.shape[1]) if up else (weight.shape[1], weight.shape[0])
+    if x.shape[-1] != ci:
+        raise ValueError(f"x has {x.shape[-1]} channels, weight expects {ci}")
+    if ci % 16 or co % 16 or ci == 0 or co == 0:
+        raise ValueError(f"{name} needs Ci and Co multiples of 16")
+    if min(x.shape[:3]) < 1 or (not up and (x.shape[1] % 2 or x.shape[2] % 2)):
+        raise ValueError(f"{name} needs a non-empty map" + ("" if up else " of even H and W"))
+    if x.dtype not in C.ACT_DTYPES:
+        raise ValueError(f"x must be bf16 or fp16, got {x.dtype}")
+    if weight.dtype != torch.float32:
+        raise ValueError("weight must be the fp32 master tensor")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != co):
+        raise ValueError("bias must be fp32 [Co]")
+    return ci, co, k
+
+
+def _s2_epilogue(bias: Optional[torch.Tensor], relu: bool, co: int, device):
+    if bias is None:
+        if relu:
+            return torch.zeros(co, dtype=torch.float32, device=device), C.EPI_BIAS_RELU
+        return None, C.EPI_NONE
+    return bias.detach().contiguous(), (C.EPI_BIAS_RELU if relu else C.EPI_BIAS)
+
+
+def _s2_dz(dy: torch.Tensor, y: torch.Tensor, relu: bool) -> torch.Tensor:
+    dz = dy.to(y.dtype)
+    if relu:
+        dz = torch.where(y > 0, dz, torch.zeros((), dtype=dz.dtype, device=dz.device))
+    return dz.contiguous()
+
+
+@torch.library.custom_op(f"{_LIB}::conv2d_down2_nhwc", mutates_args=())
+def conv2d_down2_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                      relu: bool = True) -> torch.Tensor:
+    ci, co, k = _s2_check(x, weight, bias, False)
+    x = x.contiguous()
+    bias, epi = _s2_epilogue(bias, relu, co, x.device)
+    return C.conv_down2(x, C.pack_weight_fwd(weight, x.dtype), bias, ksize=k, epi=epi)
+
+
+@conv2d_down2_nhwc.register_fake
+def _(x, weight, bias, relu=True):
+    _s2_check(x, weight, bias, False)
+    return x.new_empty(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, weight.shape[0])
+
+
+@torch.library.custom_op(f"{_LIB}::conv2d_down2_nhwc_backward", mutates_args=())
+def conv2d_down2_nhwc_backward(dy: torch.Tensor, x: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, relu: bool,
+                               need_bias: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of conv2d_down2_nhwc; dbias is an empty tensor when need_bias is False."""
+    co, ci, k, _ = weight.shape
+    dz = _s2_dz(dy, y, relu)
+    # the data gradient is the transposed conv Co -> Ci whose weight, in nn.ConvTranspose2d's layout, is `weight`
+    dx = C.conv_up2(dz, C.pack_weight_up(weight, x.dtype), None, ksize=k, epi=C.EPI_NONE)
+    dw = torch.empty(co, ci, k, k, dtype=torch.float32, device=x.device)
+    db = torch.empty(co if need_bias else 0, dtype=torch.float32, device=x.device)
+    C.conv_s2_wgrad(dz, x.contiguous(), dw, db if need_bias else None, ksize=k, bias_of="small")
+    return dx, dw, db
+
+
+@conv2d_down2_nhwc_backward.register_fake
+def _(dy, x, y, weight, relu, need_bias):
+    return (x.new_empty(x.shape), weight.new_empty(weight.shape),
+            weight.new_empty(weight.shape[0] if need_bias else 0))
+
+
+@torch.library.custom_op(f"{_LIB}::conv_transpose2d_up2_nhwc", mutates_args=())
+def conv_transpose2d_up2_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                              relu: bool = True) -> torch.Tensor:
+    ci, co, k = _s2_check(x, weight, bias, True)
+    x = x.contiguous()
+    bias, epi = _s2_epilogue(bias, relu, co, x.device)
+    return C.conv_up2(x, C.pack_weight_up(weight, x.dtype), bias, ksize=k, epi=epi)
+
+
+@conv_transpose2d_up2_nhwc.register_fake
+def _(x, weight, bias, relu=True):
+    _s2_check(x, weight, bias, True)
+    return x.new_empty(x.shape[0], 2 * x.shape[1], 2 * x.shape[2], weight.shape[1])
+
+
+@torch.library.custom_op(f"{_LIB}::conv_transpose2d_up2_nhwc_backward", mutates_args=())
+def conv_transpose2d_up2_nhwc_backward(dy: torch.Tensor, x: torch.Tensor, y: torch.Tensor, weight: torch.Tensor,
+                                       relu: bool, need_bias: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of conv_transpose2d_up2_nhwc; dbias is an empty tensor when need_bias is False."""
+    ci, co, k, _ = weight.shape
+    dz = _s2_dz(dy, y, relu)
+    # the data gradient is the down-sampling conv Co -> Ci with weight[ci][co] as its [out][in] weight
+    dx = C.conv_down2(dz, C.pack_weight_fwd(weight, x.dtype), None, ksize=k, epi=C.EPI_NONE)
+    dw = torch.empty(ci, co, k, k, dtype=torch.float32, device=x.device)
+    db = torch.empty(co if need_bias else 0, dtype=torch.float32, device=x.device)
+    C.conv_s2_wgrad(x.contiguous(), dz, dw, db if need_bias else None, ksize=k, bias_of="big")
+    return dx, dw, db
+
+
+@conv_transpose2d_up2_nhwc_backward.register_fake
+def _(dy, x, y, weight, relu, need_bias):
+    return (x.new_empty(x.shape), weight.new_empty(weight.shape),
+            weight.new_empty(weight.shape[1] if need_bias else 0))
+
+
+def _s2_setup(ctx, inputs, output):
+    x, weight, bias, relu = inputs
+    ctx.save_for_backward(x, weight, output)
+    ctx.relu, ctx.has_bias = relu, bias is not None
+
+
+def _down2_bwd(ctx, dy):
+    x, weight, y = ctx.saved_tensors
+    dx, dw, db = conv2d_down2_nhwc_backward(dy, x, y, weight, ctx.relu, ctx.has_bias)
+    return dx, dw, (db if ctx.has_bias else None), None
+
+
+def _up2_bwd(ctx, dy):
+    x, weight, y = ctx.saved_tensors
+    dx, dw, db = conv_transpose2d_up2_nhwc_backward(dy, x, y, weight, ctx.relu, ctx.has_bias)
+    return dx, dw, (db if ctx.has_bias else None), None
+
+
+conv2d_down2_nhwc.register_autograd(_down2_bwd, setup_context=_s2_setup)
+conv_transpose2d_up2_nhwc.register_autograd(_up2_bwd, setup_context=_s2_setup)
 
 
 @torch.library.custom_op(f"{_LIB}::relu_max_pool2x2", mutates_args=())
@@ -573,6 +718,43 @@ class Conv2dThinNHWC(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return torch.ops.cannet.conv2d_thin_nhwc(x, self.weight, self.bias, self.dilation, self.relu, self.fp32_out)
+
+
+class Conv2dDown2NHWC(nn.Module):
+    """nn.Conv2d(ci, co, k, stride=2, padding=(k - 1) // 2) [+ ReLU] on NHWC 16-bit activations of even H and W
+    (``torch.ops.cannet.conv2d_down2_nhwc``), k = 1 .. 4.  Parameters are fp32 in the PyTorch layout, so ``state_dict``
+    is interchangeable with that nn.Conv2d's."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: int = 3, bias: bool = True, relu: bool = True):
+        super().__init__()
+        if not 1 <= kernel_size <= C.S2_MAX_K:
+            raise ValueError(f"kernel_size must be 1 .. {C.S2_MAX_K}")
+        self.relu = relu
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+        self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
+        nn.init.normal_(self.weight, std=0.01)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return torch.ops.cannet.conv2d_down2_nhwc(x, self.weight, self.bias, self.relu)
+
+
+class ConvTranspose2dUp2NHWC(nn.Module):
+    """nn.ConvTranspose2d(ci, co, k, stride=2, padding=(k - 1) // 2, output_padding=k % 2) [+ ReLU] on NHWC 16-bit
+    activations (``torch.ops.cannet.conv_transpose2d_up2_nhwc``), k = 1 .. 4: the output is exactly twice the input.
+    Parameters are fp32 in nn.ConvTranspose2d's layout ([in, out, k, k]), so ``state_dict`` is interchangeable with
+    it."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size: int = 2, bias: bool = True, relu: bool = True):
+        super().__init__()
+        if not 1 <= kernel_size <= C.S2_MAX_K:
+            raise ValueError(f"kernel_size must be 1 .. {C.S2_MAX_K}")
+        self.relu = relu
+        self.weight = nn.Parameter(torch.empty(in_channels, out_channels, kernel_size, kernel_size))
+        self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
+        nn.init.normal_(self.weight, std=0.01)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return torch.ops.cannet.conv_transpose2d_up2_nhwc(x, self.weight, self.bias, self.relu)
 
 
 class BatchNorm2dNHWC(nn.Module):
