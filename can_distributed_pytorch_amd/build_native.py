@@ -101,7 +101,7 @@ NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"bayes.hip": NO_PACKED_FP32, "otloss.hip": NO_PACKED_FP32, "conv_small.hip": NO_PACKED_FP32,
               "batchnorm.hip": NO_PACKED_FP32, "conv_thin.hip": NO_PACKED_FP32,
               "resample.hip": NO_PACKED_FP32, "conv_large.hip": NO_PACKED_FP32,
-              "conv_stride2.hip": NO_PACKED_FP32}
+              "conv_stride2.hip": NO_PACKED_FP32, "groupnorm.hip": NO_PACKED_FP32}
 
 
 def _compile(src: str, headers, verbose=False, asan: bool = False) -> str:

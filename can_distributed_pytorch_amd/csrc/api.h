@@ -149,6 +149,26 @@ int can_bn_forward(const void* x, void* y, const float* gamma, const float* beta
 int can_bn_backward(const void* dy, const void* x, const void* y, const float* gamma, const float* stats, double* part,
                     int S, float* fin, void* dx, long long M, int C, int training, int relu, int dt, void* stream);
 
+// groupnorm.hip: group / instance normalisation (+ ReLU) of an NHWC 16-bit map x [N][H][W][C] (C % 8 == 0, G groups of
+// cg = C / G channels, statistics per (sample, group)), fp32 parameters, stats [N][G][3] = (mean, biased var, rstd).
+// Plans: groupnorm_plan.h.  form: 0 planned, 1 streamed (double partials part [N][S][2][C], S pixel slices of a sample,
+// slices = 0: planned, else 1 .. 65535), 2 resident (a block keeps a sample's [H W][bundle] tile in LDS; S = 1).
+// Refused before any launch: -2 C or G, -3 H W cg < 2, -4 eps negative or not finite, -5 a map beyond the indexing
+// (N > 65535 or more than 2^48 elements), -6 a form or slice count out of range or a missing workspace, -7 a null
+// operand, -8 a forced resident form whose tiles do not fit the LDS, -20 dt.
+// out4 = (form, S, bundle channels: 0 when the resident form cannot serve the shape, channel spans), lds = the
+// resident block's LDS bytes; backward: the plan of can_gn_backward (two tiles per block)
+int can_gn_plan(int N, int H, int W, int C, int G, int backward, int form, int slices, int* out4, long long* lds);
+// a = gamma * rstd, b = fma(-mean, a, beta) per (sample, channel); y = f2h(fma(x, a, b)), clamped at 0 with relu.
+// Streamed: part [N][S][2][C] doubles and ab [N][2][C] fp32 are workspaces; the resident form needs neither.
+int can_gn_forward(const void* x, void* y, const float* gamma, const float* beta, double* part, float* ab, float* stats,
+                   int N, int H, int W, int C, int G, double eps, int relu, int dt, int form, int slices, void* stream);
+// dx = rstd (gamma dz - c1 - xhat c2), dz = dy where y > 0 (relu; y is read only then), xhat = (x - mean) rstd from the
+// forward's stats; dgb [2][C] = (dgamma, dbeta).  part [N][S][2][C] doubles (both forms), c12 [N][G][2] fp32 (streamed).
+int can_gn_backward(const void* dy, const void* x, const void* y, const float* gamma, const float* stats, double* part,
+                    float* c12, float* dgb, void* dx, int N, int H, int W, int C, int G, int relu, int dt, int form,
+                    int slices, void* stream);
+
 // resample.hip: adaptive average pool and bilinear resize of an NHWC 16-bit map [N][H][W][C] (C % 8 == 0) to
 // [N][oh][ow][C], forward and backward, fp32 arithmetic in a fixed order (plans: resample_plan.h).  Refused before any
 // launch: -2 C, -3 a size below 1, -5 an operand beyond the 32-bit indexing rule, -6 a form / staging / slice request

@@ -52,6 +52,12 @@ GPU — and an autograd formula built from the native backward kernels.
       (running_mean, running_var).  Functional: the running buffers are never written; stats = fp32 [3, C] (mean,
       biased variance, rstd), not differentiable, is what the backward and ``BatchNorm2dNHWC``'s buffer update use.
       Backward: dz = dY masked by the stored y > 0, then dgamma / dbeta and dx on the native kernels.
+  cannet::group_norm_nhwc(x, weight, bias, groups, eps, relu) -> (y, stats)
+      F.group_norm(x, groups, weight, bias, eps) [+ ReLU] of an NHWC bf16/fp16 map, C % 8 == 0, C % groups == 0, fp32
+      parameters (csrc/groupnorm.hip); groups == C is instance norm.  Statistics per (sample, group) from double sums
+      in a fixed order: stats = fp32 [N, groups, 3] (mean, biased variance, rstd), not differentiable.  No eval mode
+      and no running statistics.  Backward: dz = dY masked by the stored y > 0, then dgamma / dbeta and dx on the
+      native kernels.
   cannet::adaptive_avg_pool_nhwc(x, oh, ow) -> y
       F.adaptive_avg_pool2d of an NHWC bf16/fp16 map, C % 8 == 0, any sizes >= 1 (bins overlap when H % oh != 0,
       oh > H is legal): fp32 sum of the bin / float(count), one rounding (csrc/resample.hip).  Backward: a gather
@@ -70,7 +76,7 @@ GPU — and an autograd formula built from the native backward kernels.
       corrections are 1 - beta^step); no amsgrad, no maximize.
 
 ``Conv2dNHWC`` / ``Conv2dThinNHWC`` / ``Conv2dDown2NHWC`` / ``ConvTranspose2dUp2NHWC`` / ``BatchNorm2dNHWC`` /
-``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master parameters; ``AdaptiveAvgPool2dNHWC`` / ``ResizeBilinearNHWC`` wrap the two resampling ops.
+``GroupNorm2dNHWC`` / ``InstanceNorm2dNHWC`` / ``ReluMaxPool2x2`` are nn.Module wrappers with fp32 master parameters; ``AdaptiveAvgPool2dNHWC`` / ``ResizeBilinearNHWC`` wrap the two resampling ops.
 """
 from __future__ import annotations
 
@@ -82,6 +88,7 @@ import torch.nn as nn
 from . import _ext
 from . import batchnorm as BN
 from . import conv as C
+from . import groupnorm as GN
 from . import resample as RS
 
 _LIB = "cannet"
@@ -498,6 +505,68 @@ def _bn_bwd(ctx, dy, dstats):
 batch_norm_nhwc.register_autograd(_bn_bwd, setup_context=_bn_setup)
 
 
+def _gn_check(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, groups: int) -> Tuple[int, int]:
+    if x.dim() != 4:
+        raise ValueError("x must be NHWC [N,H,W,C]")
+    n, h, w, c = x.shape
+    if c == 0 or c % 8:
+        raise ValueError("cannet::group_norm_nhwc needs C a multiple of 8")
+    if groups < 1 or c % groups:
+        raise ValueError(f"groups={groups} must divide C={c}")
+    if h * w * (c // groups) < 2:
+        raise ValueError("group norm needs more than one value per (sample, group)")
+    if x.dtype not in C.ACT_DTYPES:
+        raise ValueError(f"x must be bf16 or fp16, got {x.dtype}")
+    for t, name in ((weight, "weight"), (bias, "bias")):
+        if t.dtype != torch.float32 or t.numel() != c:
+            raise ValueError(f"{name} must be fp32 [{c}]")
+    return n, c
+
+
+@torch.library.custom_op(f"{_LIB}::group_norm_nhwc", mutates_args=())
+def group_norm_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, groups: int, eps: float = 1e-5,
+                    relu: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    _gn_check(x, weight, bias, groups)
+    return GN.gn_forward(x.contiguous(), weight, bias, groups, eps, relu)
+
+
+@group_norm_nhwc.register_fake
+def _(x, weight, bias, groups, eps=1e-5, relu=True):
+    n, _ = _gn_check(x, weight, bias, groups)
+    return x.new_empty(x.shape), x.new_empty(n, groups, 3, dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::group_norm_nhwc_backward", mutates_args=())
+def group_norm_nhwc_backward(dy: torch.Tensor, x: torch.Tensor, y: torch.Tensor, weight: torch.Tensor,
+                             stats: torch.Tensor, groups: int,
+                             relu: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of group_norm_nhwc."""
+    dx, dg, db = GN.gn_backward(dy.to(x.dtype).contiguous(), x.contiguous(), y, weight, stats, groups, relu)
+    return dx, dg.clone(), db.clone()           # dg / db are rows of one workspace tensor: outputs own their memory
+
+
+@group_norm_nhwc_backward.register_fake
+def _(dy, x, y, weight, stats, groups, relu):
+    return x.new_empty(x.shape), weight.new_empty(weight.shape), weight.new_empty(weight.shape)
+
+
+def _gn_setup(ctx, inputs, output):
+    x, weight, _, groups, _, relu = inputs
+    y, stats = output
+    ctx.save_for_backward(x, y, weight, stats)
+    ctx.mark_non_differentiable(stats)
+    ctx.groups, ctx.relu = groups, relu
+
+
+def _gn_bwd(ctx, dy, dstats):
+    x, y, weight, stats = ctx.saved_tensors
+    dx, dg, db = group_norm_nhwc_backward(dy, x, y, weight, stats, ctx.groups, ctx.relu)
+    return dx, dg, db, None, None, None
+
+
+group_norm_nhwc.register_autograd(_gn_bwd, setup_context=_gn_setup)
+
+
 def _resample_check(x: torch.Tensor, oh: int, ow: int) -> None:
     if x.dim() != 4:
         raise ValueError("x must be NHWC [N,H,W,C]")
@@ -783,6 +852,36 @@ class BatchNorm2dNHWC(nn.Module):
                 self.running_mean.lerp_(stats[0], f)
                 self.running_var.lerp_(stats[1] * (m / (m - 1)), f)
         return y
+
+
+class GroupNorm2dNHWC(nn.Module):
+    """nn.GroupNorm(num_groups, num_channels) [+ ReLU] on NHWC 16-bit activations
+    (``torch.ops.cannet.group_norm_nhwc``).  Parameters carry nn.GroupNorm's names and shapes, so ``state_dict`` is
+    interchangeable with it; with ``affine=False`` the ones / zeros the op reads are non-persistent buffers."""
+
+    def __init__(self, num_groups: int, num_channels: int, eps: float = 1e-5, affine: bool = True, relu: bool = True):
+        super().__init__()
+        if num_groups < 1 or num_channels % num_groups:
+            raise ValueError("num_channels must be divisible by num_groups")
+        self.num_groups, self.num_channels, self.eps, self.affine, self.relu = num_groups, num_channels, eps, affine, relu
+        if affine:
+            self.weight = nn.Parameter(torch.ones(num_channels))
+            self.bias = nn.Parameter(torch.zeros(num_channels))
+        else:
+            self.register_buffer("weight", torch.ones(num_channels), persistent=False)
+            self.register_buffer("bias", torch.zeros(num_channels), persistent=False)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return torch.ops.cannet.group_norm_nhwc(x, self.weight, self.bias, self.num_groups, self.eps, self.relu)[0]
+
+
+class InstanceNorm2dNHWC(GroupNorm2dNHWC):
+    """nn.InstanceNorm2d(num_features, affine=..., track_running_stats=False) [+ ReLU] on NHWC 16-bit activations:
+    group norm with one channel per group (SANet's layer after every conv).  ``state_dict`` equals nn.InstanceNorm2d's:
+    empty with ``affine=False`` (the default), weight and bias otherwise.  No running statistics."""
+
+    def __init__(self, num_features: int, eps: float = 1e-5, affine: bool = False, relu: bool = True):
+        super().__init__(num_features, num_features, eps, affine, relu)
 
 
 class ReluMaxPool2x2(nn.Module):
